@@ -1,6 +1,12 @@
 """Benchmark: B' synthesis throughput (B' pixels/s) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the result line (value,
+ms_per_step, dtype, configuration); --dump-outputs DIR also writes what the last timed step
+returned as DIR/<name>.npy.  --full adds, after the timed steps, everything else: a second
+pass with HIP events (roofline, matcher statistics), the result checks, the CPU baseline,
+the HBM-bound kernels' rates and the LSH quality.
 
 One STEP = the whole hot path over one synthetic analogy, from the luminance images
 resident in HBM to B' and the (s, im) index maps in HBM: Gaussian pyramids of A, A', B
@@ -192,27 +198,31 @@ class Job:
                 'mean_dist_ratio': float(ld.mean().item() / max(ed.mean().item(), 1e-300)),
                 'params': dict(self.lsh)}
 
+    def level_shapes(self, img):
+        """Shapes of an image's pyramid levels, coarsest first (level l at index l)."""
+        n = ip.num_layers(img.shape[0], img.shape[1], cfg.n_sm, self.levels)
+        out = [tuple(img.shape)]
+        for _ in range(n):
+            out.append(((out[-1][0] + 1) // 2, (out[-1][1] + 1) // 2))
+        return out[::-1]
+
     def sharded_levels(self, nranks):
         """Levels whose database is sharded over nranks ranks (image_analogies.shard_level)."""
-        def shapes(img):
-            n = ip.num_layers(img.shape[0], img.shape[1], cfg.n_sm, self.levels)
-            out = [tuple(img.shape)]
-            for _ in range(n):
-                out.append(((out[-1][0] + 1) // 2, (out[-1][1] + 1) // 2))
-            return out[::-1]
-        al = shapes(self.A)
+        al = self.level_shapes(self.A)
         return sum(ia.shard_level(al[l][0] * al[l][1], nranks) for l in range(1, self.max_levels))
+
+    def finest_db_rows(self, rank, nranks, sharded):
+        """Rows of the largest level database one rank screens: the level's A' pixels, or the
+        rank's share of them where the level is sharded (image_analogies.shard_level)."""
+        al = self.level_shapes(self.A)
+        rows = [al[l][0] * al[l][1] for l in range(1, self.max_levels)]
+        return max(ia.shard_rows(n, rank, nranks)[1] if sharded and ia.shard_level(n, nranks) else n
+                   for n in rows)
 
     def algorithmic_pairs(self):
         """sum over synthesized levels of q_l * N_l (the matcher's (query, row) pairs);
         pyramids are aligned from the coarse end as in image_analogies.py:82-86."""
-        def shapes(img):
-            n = ip.num_layers(img.shape[0], img.shape[1], cfg.n_sm, self.levels)
-            out = [tuple(img.shape)]
-            for _ in range(n):
-                out.append(((out[-1][0] + 1) // 2, (out[-1][1] + 1) // 2))
-            return out[::-1]
-        bl, al = shapes(self.B), shapes(self.A)
+        bl, al = self.level_shapes(self.B), self.level_shapes(self.A)
         return sum(bl[l][0] * bl[l][1] * al[l][0] * al[l][1] for l in range(1, self.max_levels))
 
 
@@ -376,6 +386,38 @@ def hbm_kernels(dev, reps=20):
     return out
 
 
+# --dump-outputs: array bytes of all files of a run together (with the .npy headers < 64 MB)
+DUMP_BYTES = 60 * 1000 * 1000
+
+
+def last_outputs(last, budget):
+    """--dump-outputs: what one step returned, on the host, by file name.  last: (job,
+    {level: (s, im)}) per job.  Per job (named by its seed) and synthesized level: B' as the
+    step left it (float64), the source pixel map s (n x 2) and the image map im as float32
+    (exact: pixel coordinates and image numbers).  More than `budget` bytes in all: the same
+    fraction of every array's elements, a fixed seeded choice in index order."""
+    arrs = {}
+    for jb, out in last:
+        for l in sorted(out):
+            arrs['job%d_bp%d' % (jb.seed, l)] = jb.Bp[l].cpu().numpy()
+            arrs['job%d_s%d' % (jb.seed, l)] = out[l][0].cpu().numpy().astype(np.float32)
+            arrs['job%d_im%d' % (jb.seed, l)] = out[l][1].cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > budget:
+        rs = np.random.RandomState(0)
+        for name in sorted(arrs):
+            a = arrs[name].reshape(-1)
+            keep = np.sort(rs.choice(a.size, int(a.size * budget / total), replace=False))
+            arrs[name] = a[keep]
+    return arrs
+
+
+def write_outputs(path, arrs):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
         sk.bind(('127.0.0.1', 0))
@@ -420,6 +462,13 @@ def main():
     ap.add_argument('--streams', type=int, default=4,
                     help='c5 with --batch 1: jobs run concurrently per GPU (one HIP stream + '
                          'host thread each; 4 = the HIP hardware queues per process)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run everything else the benchmark reports: '
+                         'the events pass (roofline, matcher statistics), the result checks, '
+                         'the CPU baseline, the HBM-bound kernels, the LSH quality')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write what the last timed step returned (B' and the (s, im) maps of "
+                         'every level and job) as DIR/<name>.npy, at most 64 MB in all')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=10.0,
                     help='CPU work per leg of the CPU baseline (1 thread, all threads)')
@@ -572,9 +621,11 @@ def main():
     def run_step(prof=False):
         # no per-step ia_synth_status (a host sync per step): every level folds its error
         # word into the device's sticky word, checked once after each timed pass
+        # returns (job, {level: (s, im)}) per job, as the synthesis calls returned them
         if batch > 1:
-            return run_batches(prof, check=False)
-        run_jobs(lambda jb: jb.step(comm, rank, world, prof, check=False))
+            return list(zip(jobs, run_batches(prof, check=False)))
+        order = jobs if pool is None else [j for i in range(nstreams) for j in jobs[i::nstreams]]
+        return list(zip(order, run_jobs(lambda jb: jb.step(comm, rank, world, prof, check=False))))
 
     def pass_status():
         pass_check(comm)
@@ -588,33 +639,46 @@ def main():
         if world > 1:
             dist.barrier()
         t0 = time.perf_counter()
+        last = None
         for _ in range(args.steps):
-            run_step(prof)
+            last = None               # a step's results are dropped before the next step
+            last = run_step(prof)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         dt = time.perf_counter() - t0
-        return dt, (_ia.prof_end() if prof else None)
+        return dt, (_ia.prof_end() if prof else None), last
 
     def measure():
-        # warm-up steps run profiled too; the event pool is created before any timed region
-        nev = 3 * args.steps * sum(jb.waves for jb in jobs)
-        _ia.prof_begin(nev)
-        for _ in range(args.warmup):
-            run_step(True)
-        _ia.prof_end()
+        if args.full:
+            # warm-up steps run profiled too; the event pool is created before any timed region
+            nev = 3 * args.steps * sum(jb.waves for jb in jobs)
+            _ia.prof_begin(nev)
+            for _ in range(args.warmup):
+                run_step(True)
+            _ia.prof_end()
+        else:
+            for _ in range(args.warmup):
+                run_step()
         pass_status()
-        # `value`: the product path alone; then the same K steps with the HIP events of the
-        # roofline (their cost is reported as events_overhead)
-        plain, _ = timed_pass(False)
+        # `value`: the product path alone
+        plain, _, last = timed_pass(False)
         pass_status()
-        evented, prof = timed_pass(True)
+        dump = last_outputs(last, DUMP_BYTES // world) if dumping else None
+        del last
+        if not args.full:
+            return plain, None, None, dump
+        # --full: the same K steps again with the HIP events of the roofline (their cost is
+        # reported as events_overhead)
+        evented, prof, _ = timed_pass(True)
         pass_status()
-        return plain, evented, prof
+        return plain, evented, prof, dump
 
+    # c5's jobs differ from rank to rank (each rank writes its own); else the ranks hold replicas
+    dumping = bool(args.dump_outputs) and (rank == 0 or args.config == 'c5')
     exchange_fallback = None
     try:
-        elapsed, elapsed_ev, prof = measure()
+        elapsed, elapsed_ev, prof, dump = measure()
     except _ia.ExchangeTimeout as e:
         # another rank's records never came over the device-side exchange: every rank
         # agrees, takes the RCCL exchange and measures again from scratch (every step
@@ -636,14 +700,69 @@ def main():
         _ia._EXCHANGE_FALLBACK.append(exchange_fallback)
         print('bench.py: %s; measuring again over RCCL' % exchange_fallback, file=sys.stderr, flush=True)
         comm = [_ia.exchange(rank, world, 'rccl') for _ in comm]
-        elapsed, elapsed_ev, prof = measure()
+        elapsed, elapsed_ev, prof, dump = measure()
     for cm in comm or []:
         _ia.exchange_status(cm)     # raises if a device-side exchange wait timed out
     own_elapsed = elapsed
-    t = torch.tensor([elapsed, elapsed_ev], dtype=torch.float64)
+    t = torch.tensor([elapsed, elapsed_ev or 0.0], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, elapsed_ev = float(t[0].item()), float(t[1].item())
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
+        del dump
+
+    pixels_per_step = sum(jb.pixels for jb in jobs) * (world if args.config == 'c5' else 1)
+    value = pixels_per_step * args.steps / elapsed
+    # the rotated screen (R16) runs on the fused kernel's levels of at least
+    # rot_min_rows() rows (the finest level's DB, or this rank's shard of it: level_index)
+    fin_rows = (max((p['rows'] for p in prof), default=0) if prof is not None else
+                jobs[0].finest_db_rows(rank, world, comm is not None and lsh is None))
+    rot_used = (_ia.db_rot_enabled() and lsh is None and fin_rows >= _ia.rot_min_rows() and
+                (comm is None or _ia.exchange_kind() == 'peer'))
+    result = {
+        'metric': "B' pixels/sec (brute-force match, 5-level pyramid) + MFMA util @1/2/4/8 GPU"
+                  + (' [LSH matcher]' if lsh is not None else ''),
+        'value': value,
+        'unit': "B' pixels/s",
+        'n_gpus': world,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'ms_per_step': elapsed / args.steps * 1e3,
+        'higher_is_better': True,
+        'scaling': 'weak' if args.config == 'c5' else 'strong',
+        'vs_baseline': None,
+        'dtype': ('f16 rotated split (R16 MFMA screen: %d principal components as f16 pairs, %d as '
+                  'f16, f32 accumulate) + f64 (rotation, exact rescore, pyramids)'
+                  % (_ia.lib().ia_db_rot_components(), 55 - _ia.lib().ia_db_rot_components()) if rot_used else
+                  'f16x3 split (MFMA screen, f32 accumulate) + f32 (re-screen) + f64 (exact '
+                  'rescore, pyramids)'),
+        'data': 'synthetic (gaussian-filtered noise; A\' = blur(A)); seeded',
+        'config': {'workload': args.config + ': ' + conf['name'] +
+                               (', LSH matcher' if lsh is not None else ', brute force'),
+                   'A': list(conf['A']), 'B': list(conf['B']), 'kappa': conf['k'],
+                   'levels_cap': conf['levels'], 'jobs_per_gpu': len(jobs), 'streams_per_gpu': nstreams,
+                   'jobs_per_launch': batch,
+                   'pixels_per_step': pixels_per_step,
+                   'parallelism': ('jobs%d' % world) if args.config == 'c5' else
+                                  ('db-shard%d' % world if world > 1 else 'single'),
+                   **({'exchange': _ia.exchange_kind() + (' (ranks share one GPU)' if share_gpu() else '')}
+                      if comm is not None else {})},
+        # N > 1 with DB sharding: whether a device-side exchange wait timed out and the
+        # numbers are the RCCL exchange's (null: no fallback happened)
+        **({'exchange_fallback': exchange_fallback or (_ia._EXCHANGE_FALLBACK[-1]
+                                                       if _ia._EXCHANGE_FALLBACK else None)}
+           if comm is not None else {}),
+    }
+    if not args.full:
+        # a plain run ends here: set up, warmed up, timed, and the result line
+        for cm in comm or []:
+            _ia.lib().ia_comm_destroy(cm)
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # consistency of the result (outside the timed region): B' == A'[im][s] per level and
     # identical replicas across ranks
@@ -686,8 +805,6 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         replicas_ok = bool(lo.item() == hi.item())
 
-    pixels_per_step = sum(jb.pixels for jb in jobs) * (world if args.config == 'c5' else 1)
-    value = pixels_per_step * args.steps / elapsed
     # roofline of the dominant kernel: the screen instance k_screen16<G> (G = query tiles
     # per block) with the most time over the timed steps, from the HIP events on its
     # stream around each of its launches; also the whole finest level and all levels
@@ -696,13 +813,8 @@ def main():
     # its algorithmic fraction of the f16 dense peak is capped at 1/3; the
     # MFMA pipe's utilisation is reported beside it as pipe_frac
     per_pair = 2 * 55
-    # the rotated screen (R16) on the fused kernel's levels of at least
-    # rot_min_rows() rows: 4 MFMAs x 16 K-slots = 64 slots, 128 f16 flop issued per pair; else
-    # the split-f16 screen's 3 products per feature, 330
-    # (the finest level's DB, or this rank's shard of it, holds enough rows: level_index)
-    fin_rows = max((p['rows'] for p in prof), default=0)
-    rot_used = (_ia.db_rot_enabled() and lsh is None and fin_rows >= _ia.rot_min_rows() and
-                (comm is None or _ia.exchange_kind() == 'peer'))
+    # the rotated screen (R16): 4 MFMAs x 16 K-slots = 64 slots, 128 f16 flop issued per pair;
+    # else the split-f16 screen's 3 products per feature, 330
     pipe_per_pair = 2 * _ia.lib().ia_db_rot_slots() if rot_used else 3 * 2 * 55
     inst = {}
     lv = {}
@@ -789,40 +901,8 @@ def main():
                 'screen_avg_us': screen_ms * 1e3 / max(screens, 1),
                 'source': 'HIP events around every LSH query launch of the timed steps'}
 
-    result = {
-        'metric': "B' pixels/sec (brute-force match, 5-level pyramid) + MFMA util @1/2/4/8 GPU"
-                  + (' [LSH matcher]' if lsh is not None else ''),
-        'value': value,
-        'unit': "B' pixels/s",
-        'n_gpus': world,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'ms_per_step': elapsed / args.steps * 1e3,
-        'higher_is_better': True,
-        'scaling': 'weak' if args.config == 'c5' else 'strong',
-        'vs_baseline': None,
-        'dtype': ('f16 rotated split (R16 MFMA screen: %d principal components as f16 pairs, %d as '
-                  'f16, f32 accumulate) + f64 (rotation, exact rescore, pyramids)'
-                  % (_ia.lib().ia_db_rot_components(), 55 - _ia.lib().ia_db_rot_components()) if rot_used else
-                  'f16x3 split (MFMA screen, f32 accumulate) + f32 (re-screen) + f64 (exact '
-                  'rescore, pyramids)'),
-        'data': 'synthetic (gaussian-filtered noise; A\' = blur(A)); seeded',
-        'config': {'workload': args.config + ': ' + conf['name'] +
-                               (', LSH matcher' if lsh is not None else ', brute force'),
-                   'A': list(conf['A']), 'B': list(conf['B']), 'kappa': conf['k'],
-                   'levels_cap': conf['levels'], 'jobs_per_gpu': len(jobs), 'streams_per_gpu': nstreams,
-                   'jobs_per_launch': batch,
-                   'pixels_per_step': pixels_per_step,
-                   'parallelism': ('jobs%d' % world) if args.config == 'c5' else
-                                  ('db-shard%d' % world if world > 1 else 'single'),
-                   **({'exchange': _ia.exchange_kind() + (' (ranks share one GPU)' if share_gpu() else '')}
-                      if comm is not None else {})},
+    result.update({
         'roofline': roof,
-        # N > 1 with DB sharding: whether a device-side exchange wait timed out and the
-        # numbers are the RCCL exchange's (null: no fallback happened)
-        **({'exchange_fallback': exchange_fallback or (_ia._EXCHANGE_FALLBACK[-1]
-                                                       if _ia._EXCHANGE_FALLBACK else None)}
-           if comm is not None else {}),
         'matcher': {'kind': 'lsh' if lsh is not None else 'exact',
                     'rows_rescored_fp64': sum(p['rows_rescored'] for p in prof),
                     'candidate_segments': sum(p['candidate_segments'] for p in prof),
@@ -855,7 +935,7 @@ def main():
                    # c5: every job's checksum by its seed (1000 + 3 (rank + world j)), so that
                    # any job can be compared with the same seed's run at another world size
                    **({'job_sums': job_sums} if job_sums is not None and world == 1 else {})},
-    }
+    })
     if world > 1:
         # per-rank facts, so that the first run across GPUs explains itself
         rq = pixels_per_step * args.steps // (world if args.config == 'c5' else 1)

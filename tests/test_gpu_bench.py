@@ -1,6 +1,6 @@
 """bench.py's JSON contract on the GPU (one short run per workload shape, as a child
-process like the driver's own run): the keys and types the driver and the judge read,
-the roofline object, and the result checks."""
+process like the driver's own run): the keys and types the driver and the judge read; with
+--full the roofline object and the result checks; a plain run's outputs (--dump-outputs)."""
 import json
 import os
 import subprocess
@@ -11,13 +11,19 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*args):
+def run_plain(*args):
+    """A plain run: the timed steps and the result line."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *args],
                        capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, p.stdout[-2000:]
     return json.loads(lines[0])
+
+
+def run_bench(*args):
+    """The benchmark with everything it measures and checks (--full)."""
+    return run_plain('--full', *args)
 
 
 def check_contract(d, steps, warmup):
@@ -34,6 +40,43 @@ def check_contract(d, steps, warmup):
     assert r['bound'] in ('hbm', 'mfma') and r['achieved'] > 0
     assert abs(r['frac'] - r['achieved'] / r['peak']) < 1e-9
     assert d['checks']['replicas_identical'] is True
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(gpu, tmp_path):
+    """Without --full: the result line's headline keys and none of the extra measurements;
+    --steps sets the timed steps; --dump-outputs writes the last timed step's B' (float64)
+    and (s, im) maps (float32) of every synthesized level, within 64 MB, and a second run with
+    the same arguments writes the same files bit for bit."""
+    import numpy as np
+    args = ('--gpus', '1', '--config', 'c1', '--steps', '2', '--warmup', '1')
+    d = run_plain(*args, '--dump-outputs', str(tmp_path / 'a'))
+    for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step',
+              'higher_is_better', 'scaling', 'dtype', 'config'):
+        assert k in d, k
+    for k in ('roofline', 'matcher', 'events_pass', 'checks', 'cpu_baseline', 'hbm_kernels'):
+        assert k not in d, k
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['n_gpus'] == 1
+    px = d['config']['pixels_per_step']
+    assert abs(d['value'] - px / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
+    run_plain(*args, '--dump-outputs', str(tmp_path / 'b'))
+    names = sorted(os.listdir(str(tmp_path / 'a')))
+    assert names == sorted(os.listdir(str(tmp_path / 'b')))
+    levels = sorted(int(n[len('job0_bp'):-4]) for n in names if n.startswith('job0_bp'))
+    assert levels and levels[0] == 1
+    assert names == sorted('job0_%s%d.npy' % (k, l) for k in ('bp', 's', 'im') for l in levels)
+    total = 0
+    for n in names:
+        a, b = np.load(str(tmp_path / 'a' / n)), np.load(str(tmp_path / 'b' / n))
+        assert a.dtype == (np.float64 if '_bp' in n else np.float32), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 * 1000 * 1000
+    fin = levels[-1]
+    bp, s, im = (np.load(str(tmp_path / 'a' / ('job0_%s%d.npy' % (k, fin)))) for k in ('bp', 's', 'im'))
+    assert bp.shape == (180, 117) and s.shape == (180 * 117, 2) and im.shape == (180 * 117,)
+    assert px == sum(np.load(str(tmp_path / 'a' / ('job0_im%d.npy' % l))).size for l in levels)
+    assert s.min() >= 0 and s[:, 0].max() < 180 and s[:, 1].max() < 117 and np.all(im == 0)
 
 
 @pytest.mark.gpu
@@ -71,7 +114,7 @@ def test_bench_two_ranks_sharing_the_gpu_equal_one_rank(gpu):
     checksum (the sharded synthesis is exact)."""
     one = run_bench('--config', 'c1', '--steps', '1', '--warmup', '0', '--no-cpu-baseline')
     env = dict(os.environ, IA_SHARE_GPU='1', IA_SHARD_MIN_ROWS='0')
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2',
                         '--config', 'c1', '--steps', '1', '--warmup', '0', '--no-cpu-baseline'],
                        capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -91,7 +134,7 @@ def test_bench_c4_two_ranks_sharing_the_gpu_equal_one_rank(gpu):
     over the device-side exchange, replicas identical, the 1-rank checksum, no fallback."""
     one = run_bench('--config', 'c4', '--steps', '1', '--warmup', '0', '--no-cpu-baseline')
     env = dict(os.environ, IA_SHARE_GPU='1')
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2',
                         '--config', 'c4', '--steps', '1', '--warmup', '0', '--no-cpu-baseline',
                         '--strict-exchange'],
                        capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
@@ -121,7 +164,7 @@ def test_bench_c5_two_ranks_sharing_the_gpu(gpu):
     one = run_bench('--config', 'c5', '--jobs', '6', '--steps', '1', '--warmup', '0',
                     '--no-cpu-baseline')
     env = dict(os.environ, IA_SHARE_GPU='1')
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2',
                         '--config', 'c5', '--jobs', '3', '--steps', '1', '--warmup', '0',
                         '--no-cpu-baseline'],
                        capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)

@@ -568,6 +568,49 @@ def test_pass_check_classifies_a_cascade_as_an_exchange_failure(monkeypatch):
     bench.pass_check([object()])
 
 
+def test_bench_output_dump_names_types_and_budget(tmp_path):
+    """bench.last_outputs / write_outputs (--dump-outputs) on host tensors: per job and level
+    B' as float64 and s, im as float32 with the values unchanged; over the byte budget every
+    array keeps the same fraction of its elements, the same ones on every call, in index
+    order, and the files together stay within the budget."""
+    import bench
+
+    class FakeJob:
+        def __init__(self, seed):
+            self.seed = seed
+            g = torch.Generator().manual_seed(seed)
+            self.Bp = [torch.rand((3 << l, 5 << l), dtype=torch.float64, generator=g)
+                       for l in range(3)]
+
+    def out_of(jb):
+        return {l: (torch.arange(2 * jb.Bp[l].numel(), dtype=torch.int32).reshape(-1, 2),
+                    torch.full((jb.Bp[l].numel(),), l, dtype=torch.int32)) for l in (1, 2)}
+    jobs = [FakeJob(1000), FakeJob(1003)]
+    last = [(jb, out_of(jb)) for jb in jobs]
+    whole = bench.last_outputs(last, 1 << 30)
+    assert sorted(whole) == sorted('job%d_%s%d' % (s, k, l) for s in (1000, 1003)
+                                   for k in ('bp', 's', 'im') for l in (1, 2))
+    for jb in jobs:
+        for l in (1, 2):
+            bp, s, im = (whole['job%d_%s%d' % (jb.seed, k, l)] for k in ('bp', 's', 'im'))
+            assert bp.dtype == np.float64 and s.dtype == np.float32 and im.dtype == np.float32
+            assert np.array_equal(bp, jb.Bp[l].numpy()) and s.shape == (bp.size, 2)
+            assert np.array_equal(s.ravel(), np.arange(2 * bp.size)) and np.all(im == l)
+    total = sum(a.nbytes for a in whole.values())
+    part = bench.last_outputs(last, total // 3)
+    again = bench.last_outputs(last, total // 3)
+    assert sum(a.nbytes for a in part.values()) <= total // 3
+    for name, a in part.items():
+        assert a.ndim == 1 and abs(a.size - whole[name].size / 3) <= 1
+        assert a.dtype == whole[name].dtype
+        assert np.array_equal(a, again[name])
+    s = part['job1003_s2']      # the s map's values are its own indices: a sample in index order
+    assert np.all(np.diff(s) > 0) and np.array_equal(s, whole['job1003_s2'].ravel()[s.astype(int)])
+    bench.write_outputs(str(tmp_path / 'out'), part)
+    for name, a in part.items():
+        assert np.array_equal(np.load(str(tmp_path / 'out' / (name + '.npy'))), a)
+
+
 def test_residency_rule_takes_each_levels_own_kernels():
     """the rule must take every sharded level's own fused kernel.  A non-strip
     level runs k_xwave (2 workgroups per CU: ~52 KB of LDS, ~252 VGPRs), so a CU beside a

@@ -3,6 +3,7 @@
 # ("main" = the in-tree libia.so; VARIANT = _ab/libia_VARIANT.so; BENCH_ARGS: extra bench.py args)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
+BENCH_ARGS="--full $BENCH_ARGS"     # the line printed per build reads the roofline and the checksum
 for rep in 1 2; do
     for v in "$@"; do
         if [ "$v" = main ]; then unset IA_LIB_PATH; else export IA_LIB_PATH=$PWD/_ab/libia_$v.so; fi

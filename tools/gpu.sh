@@ -47,6 +47,7 @@ smoke)
     tail -1 gpurun_out/smoke.log ;;
 bench)
     tag=$1; shift
+    set -- --full "$@"      # the summary below reads the roofline, the events pass and the checks
     timeout -k 10 900 python -u bench.py "$@" > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err \
         || { tail -20 gpurun_out/bench_$tag.err; exit 1; }
     python3 - gpurun_out/bench_$tag.json "$tag" <<'PY'
