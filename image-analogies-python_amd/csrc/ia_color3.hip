@@ -992,7 +992,7 @@ __device__ __forceinline__ double c3_tseg(float emin, float amax0, double nqq, b
     const double eps3 = nsk >= 0.0 ? r3_eps(A, nqq, (double)askip, nsk)
                                    : U32 * (900.0 * A * sqrt(nqq) + 450.0 * A * A);
     const double slack = 1e-12 * (fabs(em) + nqq + A * A);
-    force_full = eq + sc.R < -10;
+    force_full = eq + sc.R < -10 || split16_db_clamped(amax0);
     return ldexp(em + 2.0 * eps3 + slack, e2);
 }
 

@@ -38,6 +38,7 @@ __device__ __forceinline__ void rescore_thresholds(float emin, float amax0, doub
     Tseg = ldexp(em + 2.0 * eps16 + slack, e2);
     Trow = ldexp(em + eps16 + eps + slack, sc.ea);
     force_full = eq + sc.R < -10;
+    if (split16_db_clamped(amax0)) { force_full = true; Trow = INFINITY; }
 }
 
 // The 14 register groups of DB row r (split-f16, ia_split16.h): g0 = lane half 0, g1 = 1

@@ -105,7 +105,7 @@ __device__ __forceinline__ void r16_thresholds(float emin, float amax0, float as
     const double eps = r16_eps(A, nqq, (double)askip, nsk);
     const double slack = 1e-12 * (fabs(em) + nqq + A * A);
     Tseg = ldexp(em + 2.0 * eps + slack, e2);
-    force_full = eq + sc.R < -10;
+    force_full = eq + sc.R < -10 || split16_db_clamped(amax0);
 }
 
 // Per-segment skip bound (k_xstrip): segment j's rows have |rho_skip| <=
@@ -130,7 +130,7 @@ __device__ __forceinline__ void r16_tseg0(float umin, float amax0, double nqq, d
     const double eps0 = r16_eps(A, nqq, 0.0, 0.0);
     const double slack = 1e-12 * (fabs(em) + nqq + A * A) + 0x1p-23 * fabs(em);
     T0 = ldexp(em + 2.0 * eps0 + slack, e2);
-    force_full = eq + sc.R < -10;
+    force_full = eq + sc.R < -10 || split16_db_clamped(amax0);
 }
 
 // the same for k_xwave's exact stage (non-strip levels), which re-screens the candidate
@@ -151,6 +151,7 @@ __device__ __forceinline__ void r16_thresholds_rows(float emin, float amax0, flo
     Tseg = ldexp(em + 2.0 * eps + slack, e2);
     Trow = ldexp(em + eps + epsq + slack, sc.ea);
     force_full = eq + sc.R < -10;
+    if (split16_db_clamped(amax0)) { force_full = true; Trow = INFINITY; }
 }
 
 // lane-parallel query row (64 lanes): d = this lane's centred feature q'_k (lane k < 55),

@@ -53,6 +53,15 @@ __device__ __forceinline__ Split16Db split16_db_scale(float amax) {
     e = e < -60 ? -60 : (e > 60 ? 60 : e);
     return Split16Db{13 - e, e + 1};
 }
+// amax below 2^-60 or from 2^61 up: e is clamped, sa * Amax leaves [2^13, 2^14) and the scaled
+// values leave the f16 range the error bounds of the screens and of the fp32 re-screen assume
+// (DESIGN.md §4b).  The exact stage then trusts neither: it rescores every row of every
+// segment (force_full, and no re-screen cut).
+__device__ __forceinline__ bool split16_db_clamped(float amax) {
+    if (!(amax > 0.f)) return false;
+    const int e = ilogbf(amax);
+    return e < -60 || e > 60;
+}
 // query scale exponent from nq = |q'|^2: 2 |q'| sq < 2^14 and sq 2^R <= 2^15.  The same
 // function of the same fp64 nq runs in the query kernels and in k_rescore.
 __device__ __forceinline__ int split16_q_scale(double nq, int R) {

@@ -220,6 +220,73 @@ def test_c_oracle_colour_equals_numpy_oracle(seed, A, B, n_ap, k):
                 assert np.array_equal(a, b), (l, indexed)
 
 
+def _tie_cases(nch):
+    """Label-map and constant-A inputs (tests/test_gpu_fallback.py) as oracle pyramids: flat
+    regions whose rows and queries tie exactly, and a database of identical rows."""
+    import test_gpu_fallback as fb
+    if nch == 1:
+        for images in (fb.label_inputs(5, (24, 32), (20, 24), 2, band=2, patch=6, same_bg=True),
+                       fb.degenerate_inputs('const_exact', 6, (24, 32), (20, 24)),
+                       fb.degenerate_inputs('const_round', 6, (24, 32), (20, 24))):
+            yield o.setup_luminance(*images, seed=5)
+    else:
+        yield fb.colour_label_inputs(5, (24, 32), (20, 24), 2, band=2, patch=6)
+        A = np.dstack([np.full((24, 32), v) for v in (0.25, 0.5, 0.75)])
+        B = np.dstack([fb.smooth_noise(7 + 17 * ch, (20, 24)) for ch in range(3)])
+        A_pyr, Ap_list, B_pyr, _, L = fb.colour_pyramids(A, [np.full((24, 32, 3), 0.5)], B)
+        yield A_pyr, Ap_list, B_pyr, o.initialize_Bp(B_pyr, True, 7), L
+
+
+@pytest.mark.parametrize('nch', [1, 3])
+def test_c_oracle_equals_numpy_oracle_on_exact_ties(nch):
+    """The checker of the GPU full-scan tests (test_gpu_fallback.py) on its own inputs, 1 and 3
+    channels: with flat regions tying hundreds of rows exactly, and with every row of the
+    database identical, the C oracle (scan and projection index) equals the numpy oracle."""
+    w = o.compute_weights(3, 5, 12, nch)
+    for A_pyr, Ap_list, B_pyr, Bp_pyr, L in _tie_cases(nch):
+        r1 = o.synthesize(A_pyr, Ap_list, B_pyr, [b.copy() for b in Bp_pyr], L, 1.0)
+        for indexed in (False, True):
+            r2 = oc.synthesize(A_pyr, Ap_list, B_pyr, [b.copy() for b in Bp_pyr], L, 1.0, w, indexed=indexed)
+            assert set(r1) == set(r2) == set(range(1, L))
+            for l in r1:
+                for a, b in zip(r1[l], r2[l]):
+                    assert np.array_equal(a, b), (l, indexed)
+
+
+@pytest.mark.parametrize('nch', [1, 3])
+def test_oracle_index_takes_lowest_row_of_a_large_tie(nch):
+    """The projection index on a label-map level (A 128 x 160, two A' images of one
+    background: 40,960 rows, most of them one bit-identical flat row): for the flat row
+    itself, nudged copies of it and textured rows, the index returns the brute-force scan's
+    row and distance, and for the flat queries that row is the LOWEST of thousands of tied
+    rows."""
+    import test_gpu_fallback as fb
+    if nch == 1:
+        A, Aps, _ = fb.label_inputs(8, (128, 160), (8, 8), 2, band=3, patch=40, same_bg=True)
+        A_pyr = o.compute_gaussian_pyramid(A, 3, 1)
+        Ap_list = [o.compute_gaussian_pyramid(x, 3, 1) for x in Aps]
+    else:
+        A_pyr, Ap_list, _, _, _ = fb.colour_label_inputs(8, (128, 160), (8, 8), 2, band=3, patch=40, cap=1)
+    db = oc.LevelDB(1, A_pyr, Ap_list)
+    assert db.N == 40960
+    flat = db.rows[db.N - 1]
+    tied = np.flatnonzero((db.rows == flat).all(axis=1))
+    assert len(tied) > 5000 and tied[0] > 0           # (the top band: row 0 is textured)
+    rs = np.random.RandomState(9)
+    Q = np.vstack([flat[None], flat + rs.randn(8, db.D) * 1e-9, flat + rs.randn(8, db.D) * 0.05,
+                   db.rows[rs.randint(0, tied[0], 8)], db.rows[tied[rs.randint(0, len(tied), 8)]]])
+    i0, d0 = db.scan(Q)
+    assert i0[0] == tied[0] and d0[0] == 0.0 and (i0[-8:] == tied[0]).all()
+    d = np.add.reduce((db.rows - Q[3]) ** 2, axis=1)
+    assert i0[3] == np.argmin(d) and d0[3] == d.min()
+    for P in (1, 4):
+        i1, d1 = db.index(P).nn(Q)
+        assert np.array_equal(i0, i1) and np.array_equal(d0, d1), P
+    if nch == 1:
+        i2, d2 = db.nn(Q)
+        assert np.array_equal(i0, i2) and np.array_equal(d0, d2)
+
+
 # ---- LSH restatement (SURVEY §8(f)1; this build's definition, no reference code) -------
 
 def test_lsh_keys_kat():
