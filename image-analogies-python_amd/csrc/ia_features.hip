@@ -74,6 +74,27 @@ int rot_check_orthonormal(const float *rot, int n, int ld, hipStream_t st, const
     return IA_OK;
 }
 
+// The builders' precondition on the bound A (amax[0], just computed on the stream): from 2^64
+// up |a'|^2 overflows fp32, the norm slots of every DB form hold inf and scaled features can
+// overflow f16, so the exact stage's fp32 re-screen yields NaN for some rows; `e <= Trow` is
+// then false even for Trow = +inf (the clamped scale's full scan), and such a row, possibly
+// the nearest one, is never rescored.  Refused instead (one 4-byte read-back per build).
+int db_check_amax(const float *amax, hipStream_t st, const char *who) {
+    float a = 0.f;
+    IA_HIP(hipMemcpyAsync(&a, amax, sizeof a, hipMemcpyDeviceToHost, st));
+    IA_HIP(hipStreamSynchronize(st));
+    if (!(a < 0x1p64f)) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg,
+                      "%s: the level's bound A = %.3g is 2^64 or more: |a'|^2 overflows fp32 and the matcher "
+                      "would not be exact; scale the images down (a power of two keeps every result)",
+                      who, (double)a);
+        set_error(msg);
+        return IA_E_ARG;
+    }
+    return IA_OK;
+}
+
 __global__ void k_level_features(ImgPair p, int full, double *out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)p.h * p.w) return;
@@ -332,7 +353,7 @@ __global__ __launch_bounds__(256) void k_db_build_t(DbSrc src, long row0, long n
     if constexpr (NORM_ONLY) {   // the same pair as k_img_norm reads back from the row form
         const long lr = (long)blockIdx.x * 256 + threadIdx.x;
         _Float16 h, l;
-        split16f(ldexpf(my[55], s.ea - s.R), h, l);
+        split16f_sat(ldexpf(my[55], s.ea - s.R), h, l);
         if (lr < nrows)
             norm[lr] = (uint32_t)__builtin_bit_cast(uint16_t, h) | ((uint32_t)__builtin_bit_cast(uint16_t, l) << 16);
         return;
@@ -340,7 +361,7 @@ __global__ __launch_bounds__(256) void k_db_build_t(DbSrc src, long row0, long n
     _Float16 xh[IA_DP], xl[IA_DP];
 #pragma unroll
     for (int k = 0; k < IA_DP; ++k)
-        split16f(k < 55 ? ldexpf(my[k], s.ea) : ldexpf(my[55], s.ea - s.R), xh[k], xl[k]);
+        split16f_sat(k < 55 ? ldexpf(my[k], s.ea) : ldexpf(my[55], s.ea - s.R), xh[k], xl[k]);
     const long T = (long)blockIdx.x * DBT_TILES + (threadIdx.x >> 5);
     half8 *out = db16 + T * (DB16_GROUPS * 64) + (threadIdx.x & 31);
 #pragma unroll
@@ -399,7 +420,7 @@ __global__ __launch_bounds__(256) void k_db_build(DbSrc src, long row0, long nro
                 const int k = k0 + e;
                 const float v = k < 55 ? ldexpf(tr[k], s.ea) : ldexpf(tr[55], s.ea - s.R);
                 _Float16 xh, xl;
-                split16f(v, xh, xl);
+                split16f_sat(v, xh, xl);
                 o[e] = hi ? xh : xl;
             }
             out[g * 64] = o;
@@ -420,7 +441,7 @@ __global__ __launch_bounds__(256) void k_img_pad(const double *__restrict__ img,
     const double v = img[(long)symi(r - IMG_PY, h) * w + symi(q - IMG_PX, w)];
     const Split16Db s = split16_db_scale(amax[0]);
     _Float16 xh, xl;
-    split16f(ldexpf((float)(v - center[ck]), s.ea), xh, xl);
+    split16f_sat(ldexpf((float)(v - center[ck]), s.ea), xh, xl);
     out[i] = (uint32_t)__builtin_bit_cast(uint16_t, xh) | ((uint32_t)__builtin_bit_cast(uint16_t, xl) << 16);
 }
 
@@ -508,7 +529,7 @@ struct ImgBuild {
 
 __device__ __forceinline__ uint32_t split_pair(double d, int ea) {
     _Float16 xh, xl;
-    split16f(ldexpf((float)d, ea), xh, xl);
+    split16f_sat(ldexpf((float)d, ea), xh, xl);
     return (uint32_t)__builtin_bit_cast(uint16_t, xh) | ((uint32_t)__builtin_bit_cast(uint16_t, xl) << 16);
 }
 
@@ -646,7 +667,7 @@ __device__ __forceinline__ void img_tile(const ImgBuild &b, int blk, const doubl
         const long g = (long)img * b.hw + (long)y * W + x;
         if (g >= b.row0 && g < b.row0 + b.nrows) {
             _Float16 h, l;
-            split16f(ldexpf((float)n2, sc.ea - sc.R), h, l);
+            split16f_sat(ldexpf((float)n2, sc.ea - sc.R), h, l);
             nm[g - b.row0] = (uint32_t)__builtin_bit_cast(uint16_t, h) | ((uint32_t)__builtin_bit_cast(uint16_t, l) << 16);
         }
         // padded pixels: fine A (image 0), fine A', and the coarse ones at even coordinates
@@ -901,12 +922,12 @@ int ia_db_build(const IaSrcLevel *src, long row0, long nrows, const double *cent
         k_db_build_t<false><<<(unsigned)(npad / 256), 256, 0, S(stream)>>>(
             d, row0, nrows, center, amax, reinterpret_cast<half8 *>(db), nullptr);
         IA_LAUNCH_CHECK("k_db_build_t");
-        return IA_OK;
+        return db_check_amax(amax, S(stream), "ia_db_build");
     }
     k_db_build<<<(unsigned)((npad + 255) / 256), 256, 0, S(stream)>>>(d, row0, nrows, npad, center,
                                                                      amax, reinterpret_cast<half8 *>(db));
     IA_LAUNCH_CHECK("k_db_build");
-    return IA_OK;
+    return db_check_amax(amax, S(stream), "ia_db_build");
 }
 
 size_t ia_db_image_bytes(const IaSrcLevel *src, long row0, long nrows) {
@@ -959,7 +980,7 @@ int ia_db_build_image(const IaSrcLevel *src, long row0, long nrows, const double
                "ia_db_build_image: fused build shape");
         k_img_build<<<(unsigned)(bb.main_blocks + mblocks), IB_T, 0, st>>>(bb, center, amax, rng);
         IA_LAUNCH_CHECK("k_img_build");
-        return IA_OK;
+        return db_check_amax(amax, st, "ia_db_build_image");
     }
     if (!db) {   // no row form: amax here, from the scratch section's partials
         const int rc = launch_db_amax(src, d, center, amax,
@@ -988,7 +1009,7 @@ int ia_db_build_image(const IaSrcLevel *src, long row0, long nrows, const double
                                                                     const_cast<uint32_t *>(v.norm.get()));
         IA_LAUNCH_CHECK("k_db_build_t<norm>");
     }
-    return IA_OK;
+    return db_check_amax(amax, st, "ia_db_build_image");
 }
 
 int ia_center_fill(double *center, double mA, double mAp, void *stream) {

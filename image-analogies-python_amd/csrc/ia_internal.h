@@ -13,6 +13,8 @@ namespace ia {
 // n x n rotation rot[k * ld + j] (device memory, ordered on st) read back once per level, and
 // ||V_f^T V_f - I||_F (>= the spectral norm, which equals ||V_f V_f^T - I||'s) <= 2 sqrt(n) u.
 int rot_check_orthonormal(const float *rot, int n, int ld, hipStream_t st, const char *who);
+// IA_E_ARG if the bound A just computed on st (amax[0]) is 2^64 or more (|a'|^2 overflows fp32)
+int db_check_amax(const float *amax, hipStream_t st, const char *who);
 
 // ---- database chunking (shared by ia_db_build, the screen and the exact stage) ------
 // A screen workgroup owns one chunk of ch rows (32-row tiles, 4-tile stages).  ch is

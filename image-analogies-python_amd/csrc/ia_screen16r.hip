@@ -714,7 +714,7 @@ __global__ __launch_bounds__(256) void k_db_build_rot(DbSrc src, long row0, long
                 const float r32 = (float)kk[e];
                 if (j >= R16_P) sk += (double)r32 * (double)r32;
                 _Float16 h, l;
-                split16f(ldexpf(r32, sc.ea), h, l);
+                split16f_sat(ldexpf(r32, sc.ea), h, l);
                 const int s = R16_M0 + j;
                 o[((s & 15) >> 3) * R16_MFMA + (s >> 4)][s & 7] = h;
                 if (j < R16_P) {
@@ -725,7 +725,7 @@ __global__ __launch_bounds__(256) void k_db_build_rot(DbSrc src, long row0, long
             }
         }
         _Float16 nh, nl;
-        split16f(ldexpf((float)n2, sc.ea - sc.R), nh, nl);
+        split16f_sat(ldexpf((float)n2, sc.ea - sc.R), nh, nl);
         o[((R16_NL & 15) >> 3) * R16_MFMA + (R16_NL >> 4)][R16_NL & 7] = nl;
         o[((R16_NH & 15) >> 3) * R16_MFMA + (R16_NH >> 4)][R16_NH & 7] = nh;
 #pragma unroll
@@ -973,7 +973,7 @@ int ia_db_build_rot(const IaSrcLevel *src, long row0, long nrows, const double *
         reinterpret_cast<const float *>(askseg), amax, nseg,
         reinterpret_cast<unsigned char *>(tail + r16_askc_off(nrows)));
     IA_LAUNCH_CHECK("k_askseg_codes");
-    return IA_OK;
+    return db_check_amax(amax, st, "ia_db_build_rot");
 }
 
 /* diagnostics: one R16 screen of M fp64 query rows (IA_DP each) over a rotated DB ->

@@ -83,6 +83,15 @@ __device__ __forceinline__ void split16f(float x, _Float16 &h, _Float16 &l) {
     h = (_Float16)x;
     l = (_Float16)(x - (float)h);   // x - h is exact in f32
 }
+// The DB builders' split: split16f with |x| first clipped to the largest f16 (65504).  In range
+// (sa A < 2^14) nothing changes.  Under the clamped scale (split16_db_clamped, amax from 2^61
+// up) a scaled norm slot or feature can pass 2^16; h = inf, l = x - inf = -inf would then read
+// back as h + l = NaN in the exact stage's fp32 re-screen, whose `e <= Trow` is false for NaN
+// even with Trow = +inf: the row would never be rescored.  The clipped value's size means
+// nothing there (force_full: every row is rescored in fp64); it only has to stay finite.
+__device__ __forceinline__ void split16f_sat(float x, _Float16 &h, _Float16 &l) {
+    split16f(fminf(fmaxf(x, -65504.f), 65504.f), h, l);
+}
 __device__ __forceinline__ void split16d(double x, _Float16 &h, _Float16 &l) {
     const float xf = (float)x;      // |x - xf| <= 2^-24 |x|: part of the 4u split budget
     h = (_Float16)xf;

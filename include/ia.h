@@ -98,7 +98,11 @@ int ia_level_features_f64(const double *sm, int hs, int ws, const double *lg, in
  * is exact in fp32).  Rows are padded to ia_db_rows_padded(nrows) (whole chunks of
  * ia_db_chunk_rows, a multiple of 4 chunks) by repeating the last real row.  amax (device,
  * 1 float) receives A >= max_row |a - center|, bounded from the value ranges of the level's
- * four images (max with its prior value: zero it first). */
+ * four images (max with its prior value: zero it first).
+ * Precondition of ia_db_build, ia_db_build_image and ia_db_build_rot: A < 2^64 (|a'|^2 must
+ * not overflow fp32); each reads A back after its kernels (one stream synchronisation) and
+ * returns IA_E_ARG otherwise.  From 2^61 up (and below 2^-60) the scale's exponent is clamped
+ * and the exact stage rescores every row. */
 long ia_db_rows_padded(long nrows);
 /* bytes of the db buffer ia_db_build fills: 224 B per padded row */
 size_t ia_db_bytes(long nrows);

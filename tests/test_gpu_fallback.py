@@ -2,8 +2,9 @@
 force_full`) against the scanline C oracle: label-map inputs whose flat regions tie over
 more than 1024 segments (the full scan), over exactly 1024 (the last slist slot, no full
 scan) and over the padded chunks of a linear image-form level; and constant or
-near-constant A images (amax == 0, the ilogb clamp of split16_db_scale, a zero covariance
-for the R16 rotation, force_full on every query).  Every form of the exact stage runs them;
+near-constant A images (amax == 0, the ilogb clamp of split16_db_scale at both ends: an
+analogy times 1e-25 and one times 2^62, a zero covariance for the R16 rotation, force_full on
+every query).  Every form of the exact stage runs them;
 B', s, im and the approximate pick of every pixel equal the oracle's bit for bit, and the
 profile's full_scans proves the branch ran.
 
@@ -80,7 +81,7 @@ def colour_pyramids(A, Aps, B, cap=None):
     return A_pyr, Ap_list, B_pyr, o.initialize_Bp(B_pyr, False), L
 
 
-DEGENERATE = ('near', 'const_exact', 'const_round', 'tiny', 'scaled')
+DEGENERATE = ('near', 'const_exact', 'const_round', 'tiny', 'scaled', 'huge')
 
 
 def degenerate_inputs(kind, seed, A_shape, B_shape):
@@ -89,7 +90,11 @@ def degenerate_inputs(kind, seed, A_shape, B_shape):
     'const_round' A = 0.3, A' = 0.8 (the means round: amax ~ 1e-15); 'tiny' 1e-25 smooth_noise
     (ilogb(amax) < -60: the clamp of split16_db_scale).  B is smooth_noise in [0, 1].  'scaled':
     an ordinary analogy with EVERY image times 1e-25 (the clamp with queries as small as the
-    rows, so nothing but the clamp itself can ask for the full scan)."""
+    rows, so nothing but the clamp itself can ask for the full scan).  'huge': huge_inputs (an
+    analogy with every image times a power of two that puts amax at 2^61 or above: the upper
+    clamp)."""
+    if kind == 'huge':
+        return huge_inputs(seed, A_shape, B_shape)[:3]
     if kind == 'scaled':
         A, Aps, B = analogy_inputs(seed, A_shape, B_shape, 1)
         return A * 1e-25, [Aps[0] * 1e-25], B * 1e-25
@@ -103,6 +108,24 @@ def degenerate_inputs(kind, seed, A_shape, B_shape):
         assert kind == 'tiny'
         A, Ap = 1e-25 * smooth_noise(seed, A_shape), 1e-25 * smooth_noise(seed + 7, A_shape)
     return A, [Ap], smooth_noise(seed + 1, B_shape)
+
+
+def huge_inputs(seed, A_shape, B_shape):
+    """(A, [A'], B, s): an analogy under a 1-level pyramid cap with every image times the power
+    of two s, the smallest with max |A - mean A| s >= 2^61 (a lower bound of amax, whose
+    exponent split16_db_scale then clamps at 60).  assert_forced also wants image_range_bound s
+    < 2^63.9 (|a'|^2 stays finite in fp32), and image_range_bound >= sqrt(34) max |A - mean A|:
+    the admissible s span less than a binade.  So A is smooth noise of sigma 4 stretched
+    about its median and clipped to [0, 1] (mean about 0.5: max |A - mean A| just above 0.5),
+    A' a quarter of its blur (a small share of the bound), and only the finest level runs (a
+    coarser level's narrower range would need a larger s)."""
+    from scipy.ndimage import gaussian_filter
+    x = smooth_noise(seed, A_shape, 4.0)
+    A = np.clip(0.5 + 4.0 * (x - np.median(x)), 0.0, 1.0)
+    Ap = 0.25 * gaussian_filter(A, 1.0)
+    B = smooth_noise(seed + 1, B_shape)
+    s = 2.0 ** np.ceil(61 - np.log2(np.abs(A - A.mean()).max()))
+    return A * s, [Ap * s], B * s, s
 
 
 # ---- reference-only helpers (numpy and the C oracle; no GPU) ----------------------------------
@@ -246,8 +269,12 @@ def lum_case(name):
         else:
             kind, size = name.split('@')
             shapes = {'small': ((40, 52), (24, 31), None), 'strip': ((256, 512), (12, 30), 1)}[size]
-            c = LumCase(degenerate_inputs(kind, 93, shapes[0], shapes[1]), shapes[2], 1.0, 93, tie=False,
-                        bp_scale=1e-25 if kind == 'scaled' else None)
+            if kind == 'huge':      # (the finest level only: huge_inputs)
+                A, Aps, B, sc = huge_inputs(93, shapes[0], shapes[1])
+                c = LumCase((A, Aps, B), 1, 1.0, 93, tie=False, bp_scale=sc)
+            else:
+                c = LumCase(degenerate_inputs(kind, 93, shapes[0], shapes[1]), shapes[2], 1.0, 93, tie=False,
+                            bp_scale=1e-25 if kind == 'scaled' else None)
         _CASES[name] = c
     return _CASES[name]
 
@@ -423,14 +450,23 @@ def image_range_bound(A_pyr, Ap_list, level):
     return float(np.sqrt(34 * uA * uA + 21 * uAp * uAp))
 
 
-FORCED = ('near', 'tiny', 'scaled')
+FORCED = ('near', 'tiny', 'scaled', 'huge')
 
 
 def assert_forced(case, kind, rec, level):
     """force_full's reference-only precondition (U 2^25 < min |q - c|; 'scaled': amax <= U <
-    2^-60, the clamp of split16_db_scale), then full_scans == the level's pixel count."""
+    2^-60, the clamp of split16_db_scale; 'huge': 2^61 <= max |A - mean A| <= amax <= U <
+    2^63.9, the upper clamp with |a'|^2 finite in fp32), then full_scans == the level's pixel
+    count."""
     A_pyr, Ap_list = case.pyr[0], case.pyr[1]
     U = image_range_bound(A_pyr, Ap_list, level)
+    if kind == 'huge':
+        lo = float(np.abs(A_pyr[level] - A_pyr[level].mean()).max())
+        print('force_full [huge] level %d: max |A - mean A| 2^%.2f, U 2^%.2f, full_scans %d of %d' % (
+            level, np.log2(lo), np.log2(U), rec['full_scans'], case.queries[level]))
+        assert lo >= 2.0 ** 61 and U < 2.0 ** 63.9
+        assert rec['full_scans'] == case.queries[level]
+        return
     if kind == 'scaled':
         print('force_full [scaled] level %d: U 2^%.1f, full_scans %d of %d' % (
             level, np.log2(U), rec['full_scans'], case.queries[level]))
@@ -451,7 +487,8 @@ def test_degenerate_A_strip_level_vs_oracle(gpu, form, kind, name):
     """A 256 x 512 (131,072 rows: a strip level where the rotated DB applies), constant or
     near-constant: every form equals the oracle; the near-constant and 1e-25 inputs force a
     full scan of every query, and so does an ordinary analogy scaled by 1e-25 (amax < 2^-60:
-    the clamped scale voids the screens' error bounds)."""
+    the clamped scale voids the screens' error bounds) or by 2^62 ('huge': amax >= 2^61, the
+    upper clamp; the scaled norm slots pass the f16 range and are clipped by the builders)."""
     case = lum_case(kind + '@strip')
     form(name)
     rec = run_profiled(case)
@@ -462,7 +499,10 @@ def test_degenerate_A_strip_level_vs_oracle(gpu, form, kind, name):
 @pytest.mark.parametrize('name', ['xwave', 'rescore', 'worklist'])
 @pytest.mark.parametrize('kind', DEGENERATE)
 def test_degenerate_A_row_levels_vs_oracle(gpu, form, kind, name):
-    """A 40 x 52, B 24 x 31, every level (row-form levels with padding)."""
+    """A 40 x 52, B 24 x 31, every level (row-form levels with padding; 'huge': the finest
+    level only, huge_inputs).  The forms here cut rows by the fp32 re-screen (e <= Trow): under
+    the upper clamp a norm slot stored as inf / -inf read back as NaN and dropped its row, the
+    nearest one included, until the builders clipped it."""
     import _ia
     import image_analogies as ia
     case = lum_case(kind + '@small')
@@ -520,4 +560,40 @@ def test_degenerate_A_match_and_rot_build(gpu, kind):
     c = idx.center.cpu().numpy()
     for m in range(M):
         ea, R, eq = _scales(float(amax[0]), float(((Q[m] - c) ** 2).sum()))
-        assert np.isfinite(segmin[m]).all() or eq + R < -10, (m, eq, R)
+        # (from 2^61 up the clamped scale lets scaled values overflow f16: split16_db_clamped
+        # full-scans every query, whatever its norm)
+        assert np.isfinite(segmin[m]).all() or eq + R < -10 or amax[0] >= 2.0 ** 61, (m, eq, R)
+
+
+def test_builders_refuse_norms_that_overflow_fp32(gpu):
+    """A 128 x 256 level times 2^70 (amax ~ 2^71.5: |a'|^2 overflows fp32, every norm slot would
+    hold inf and the fp32 re-screen NaN): ia_db_build, ia_db_build_image and ia_db_build_rot
+    each return IA_E_ARG with a message naming the limit; the unscaled level builds."""
+    import ctypes
+    import torch
+    import _ia
+    import algorithms
+    lib = _ia.lib()
+    A, Aps, _ = analogy_inputs(99, (128, 256), (8, 8), 1)
+    pyr = lambda x, sc: [dev(p * sc) for p in o.compute_gaussian_pyramid(x, 3, cap=1)]  # noqa: E731
+    ok = algorithms.level_index(pyr(A, 1.0), [pyr(Aps[0], 1.0)], 1, rows=True, rot=True)
+    assert ok.db is not None and ok.dbi is not None and ok.dbr is not None
+    A70, Ap70 = pyr(A, 2.0 ** 70), pyr(Aps[0], 2.0 ** 70)
+    keep = (A70[0].contiguous(), A70[1].contiguous(), torch.stack([Ap70[0]]), torch.stack([Ap70[1]]))
+    big = _ia.src_level(*keep)
+    st, c = _ia.stream(), _ia.ptr(ok.center)
+    calls = {
+        'ia_db_build': lambda am: lib.ia_db_build(ctypes.byref(big), 0, ok.nrows, c, _ia.ptr(ok.db), am, st),
+        'ia_db_build_image': lambda am: lib.ia_db_build_image(ctypes.byref(big), 0, ok.nrows, c, None, am,
+                                                              _ia.ptr(ok.dbi), st),
+        'ia_db_build_rot': lambda am: lib.ia_db_build_rot(ctypes.byref(big), 0, ok.nrows, c, _ia.ptr(ok.rot), am,
+                                                          _ia.ptr(ok.dbr), st),
+    }
+    for who, call in calls.items():
+        amax = torch.zeros(2, dtype=torch.float32, device='cuda')
+        rc = call(_ia.ptr(amax))
+        msg = lib.ia_last_error()
+        torch.cuda.synchronize()
+        assert rc == _ia.IA_E_ARG, who
+        assert who.encode() in msg and b'2^64' in msg, msg
+        assert float(amax[0].item()) >= 2.0 ** 64

@@ -32,8 +32,10 @@ def _level(seed, shape, cap, scale=1.0):
     return idx, As
 
 
-def _r16_vs_fp64(idx, As, Q, Ms):
-    """worst |segmin - exact| / eps_R over (query, segment) for each M of Ms"""
+def _r16_vs_fp64(idx, As, Q, Ms, tight=True):
+    """worst |segmin - exact| / eps_R over (query, segment) for each M of Ms; tight: the
+    per-segment skip bounds must also undercut the global one on average (true of the
+    principal basis on smooth data; not asked of other rotations)"""
     import _ia
     lib = _ia.lib()
     Mmax, N = max(Ms), len(As)
@@ -63,7 +65,8 @@ def _r16_vs_fp64(idx, As, Q, Ms):
     assert (skp[order].reshape(nseg, seg).max(1) <= ask_seg).all()
     ask_dec = askip * codes / 255.0
     assert (ask_dec >= ask_seg).all() and (codes <= 255).all()
-    assert ask_dec.mean() < 0.9 * askip, 'per-segment bounds tighter than the global one'
+    if tight:
+        assert ask_dec.mean() < 0.9 * askip, 'per-segment bounds tighter than the global one'
     exact = np.empty((Mmax, nseg))
     for m0 in range(0, Mmax, 64):
         E = na[:, None] - 2.0 * (a @ (Q[m0:m0 + 64] - c).T)

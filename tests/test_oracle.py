@@ -287,6 +287,100 @@ def test_oracle_index_takes_lowest_row_of_a_large_tie(nch):
         assert np.array_equal(i0, i2) and np.array_equal(d0, d2)
 
 
+# ---- the inputs of tests/test_gpu_bounds.py have teeth (numpy and the oracle only) -------------
+
+@pytest.mark.parametrize('n', [55, 165])
+def test_bound_rotations_are_what_they_claim(n):
+    """rotation_of (the stand-in for algorithms._eigh): every rotation passes the builders'
+    orthonormality check once rounded to fp32 (||V^T V - I||_F <= 2 sqrt(n) 2^-24), w is the
+    variance along each column, 'reversed' holds the principal directions by increasing
+    variance after the builders' flip, 'identity' the unit matrix, and no two coincide."""
+    import test_gpu_bounds as gb
+    X = np.random.RandomState(3).standard_normal((4 * n, n)) * np.linspace(0.1, 3.0, n)
+    C = X.T @ X / len(X)
+    held = {}
+    for kind in ('principal',) + gb.ROTATIONS:
+        w, V = gb.rotation_of(kind, C)
+        R = gb.held_rotation(V).astype(np.float64)
+        dev = np.linalg.norm(R.T @ R - np.eye(n))
+        print('rotation %s (n = %d): ||V^T V - I||_F = %.2g of %.2g' % (kind, n, dev, 2 * np.sqrt(n) * 2.0 ** -24))
+        assert dev <= 2 * np.sqrt(n) * 2.0 ** -24
+        assert np.allclose(w, np.einsum('ij,ij->j', V, C @ V), rtol=1e-9)
+        held[kind] = R
+    var = lambda R: np.einsum('ij,ij->j', R, C @ R)  # noqa: E731
+    assert (np.diff(var(held['principal'])) <= 1e-12).all()
+    assert (np.diff(var(held['reversed'])) >= -1e-12).all()
+    assert np.array_equal(held['reversed'], held['principal'][:, ::-1])
+    assert np.array_equal(held['identity'], np.eye(n))
+    kinds = sorted(held)
+    for i, a in enumerate(kinds):
+        for b in kinds[i + 1:]:
+            assert np.abs(held[a] - held[b]).max() > 0.1, (a, b)
+
+
+@pytest.mark.parametrize('data', ['smooth', 'white', 'outlier'])
+def test_bound_inputs_need_the_skip_term(data):
+    """The rotated screen restated in numpy (emulate_screen: f16 hi parts only for the
+    components >= P, exact products, the library's scales and segment order) on the 256 x 512
+    level and the queries of test_r16_bound_under_rotation: under every non-principal rotation
+    the worst |segment minimum - fp64| exceeds 2 eps_0 (the bound without its skip term), and
+    eps_R still holds it.  A kernel that dropped or understated the skip term cannot pass
+    those inputs.  Measured: smooth 50 / 27 / 31 eps_0 (reversed / identity / random; 0.70 /
+    0.41 / 0.45 eps_R), white 27 / 23 / 27 (0.49 / 0.42 / 0.49), outlier 7.9 / 2.9 / 7.7
+    (0.50 / 0.25 / 0.49); the principal basis: 6.7, 25 and 7.0 eps_0 with the worst-case
+    queries, 1.7, 12.5 and 3.8 without."""
+    import test_gpu_bounds as gb
+    lv = gb.bound_level(data)
+    order, seg = gb.segment_order(len(lv.As), *lv.A_pyr[1].shape)
+    assert len(lv.As) == 131072 and len(order) // seg == 512
+    for kind in gb.ROTATIONS:
+        V = gb.held_rotation(gb.rotation_of(kind, lv.cov())[1])
+        Q = lv.queries(kind)
+        assert Q.shape == (342, 55)
+        r = gb.emulate_screen(lv.As, lv.center, lv.amax, Q, order, seg, V)
+        err = np.abs(r['m'] - r['x'])
+        w0, wR = (err / r['eps0'][:, None]).max(), (err / r['epsR'][:, None]).max()
+        w64 = (err[:64] / r['eps0'][:64, None]).max()
+        print('emulated r16 screen [%s, %s]: A_skip / A = %.3f, worst error %.3g eps_0 (first 64 queries '
+              '%.3g), %.3g eps_R' % (data, kind, r['askip'] / lv.amax, w0, w64, wR))
+        assert w0 >= 2.0 and w64 >= 2.0
+        assert wR < 1.0
+
+
+def test_strip_case_needs_the_skip_term_end_to_end():
+    """The strip case of test_strip_synthesis_under_rotation under the reversed rotation, with
+    the oracle's own queries: for 6 of the 768 finest-level queries (at least 3 are asked) an
+    exact stage that tested m_j <= e* + 2 eps_0 would drop the true winner's segment, while
+    eps_R keeps it; the comparison with the oracle can therefore see a lost skip term."""
+    import test_gpu_bounds as gb
+    n, total = gb.affected_queries(gb.e2e_case('strip'))
+    print('strip case, reversed rotation: %d of %d queries lose their winner under eps_0 alone' % (n, total))
+    assert n >= 3
+
+
+@pytest.mark.parametrize('data', ['white', 'outlier'])
+def test_split16_inputs_stay_inside_eps16_with_flush(data):
+    """The split-f16 screen restated in numpy on the 128 x 256 level of
+    test_split16_bound_on_white_and_outlier_data, with f16 subnormals kept and flushed to
+    zero: the representation error stays below eps16 (a correct kernel passes), and on the
+    outlier data most scaled lo parts are f16 subnormals (the flush allowance is exercised)."""
+    import test_gpu_bounds as gb
+    from test_gpu_split16 import _scales
+    lv = gb.bound_level(data, (128, 256))
+    order, seg = gb.segment_order(len(lv.As), *lv.A_pyr[1].shape)
+    for flush in (False, True):
+        r = gb.emulate_screen(lv.As, lv.center, lv.amax, lv.Q, order, seg, None, flush=flush)
+        worst = (np.abs(r['m'] - r['x']) / r['eps0'][:, None]).max()
+        print('emulated split16 screen [%s, flush %s]: worst error %.3g eps16' % (data, flush, worst))
+        assert worst < 1.0
+    if data == 'outlier':
+        al = gb.f16_split(np.ldexp((lv.As - lv.center).astype(np.float32).astype(np.float64),
+                                   _scales(lv.amax, 0.0)[0]))[1]
+        sub = float(((np.abs(al) < 2.0 ** -14) & (al != 0)).mean())
+        print('outlier data: %.1f %% of the scaled lo parts are f16 subnormals' % (100 * sub))
+        assert sub > 0.5
+
+
 # ---- LSH restatement (SURVEY §8(f)1; this build's definition, no reference code) -------
 
 def test_lsh_keys_kat():
