@@ -211,12 +211,13 @@ def segment_order(N, Ah, Aw):
 class LumCase:
     """One luminance input with its oracle run (computed once per module, shared by the forms):
     per level the reference (B', s, im), the reconstructed queries' exact 1-NN, sa and
-    app_dist; for the finest level the tie counts per query in the library's segment order."""
+    app_dist; for the finest level the tie counts per query in the library's segment order.
+    setup: further arguments of o.setup_luminance (AB_weight, remap_lum, init_rand)."""
 
-    def __init__(self, images, cap, k, seed, tie=True, bp_scale=None):
+    def __init__(self, images, cap, k, seed, tie=True, bp_scale=None, setup=None):
         A, Aps, B = images
         self.k = k
-        A_pyr, Ap_list, B_pyr, Bp_pyr, L = o.setup_luminance(A, Aps, B, cap=cap, seed=seed)
+        A_pyr, Ap_list, B_pyr, Bp_pyr, L = o.setup_luminance(A, Aps, B, cap=cap, seed=seed, **(setup or {}))
         if bp_scale is not None:        # the random B' initialisation at the images' scale
             Bp_pyr = [b * bp_scale for b in Bp_pyr]
         self.pyr = A_pyr, Ap_list, B_pyr, Bp_pyr, L

@@ -28,8 +28,11 @@ def _write_png(path, img, mode):
     Image.fromarray(np.clip(np.round(img * 255), 0, 255).astype(np.uint8), mode).save(path)
 
 
-def _oracle_run(Ay, Apy, By, seed, k, color_level_fn):
-    A_pyr, Ap_list, B_pyr, Bp_pyr, L = o.setup_luminance(Ay, [Apy], By, seed=seed)
+def _oracle_run(Ay, Apy, By, seed, k, color_level_fn, setup=None):
+    """Apy: one A' image or a list of them; setup: further arguments of o.setup_luminance
+    (AB_weight, remap_lum, cap, init_rand)."""
+    Aps = list(Apy) if isinstance(Apy, (list, tuple)) else [Apy]
+    A_pyr, Ap_list, B_pyr, Bp_pyr, L = o.setup_luminance(Ay, Aps, By, seed=seed, **(setup or {}))
     As = o.create_index(A_pyr, Ap_list, L)
     w = o.compute_weights(3, 5, 12, 1)
     res = {}

@@ -79,13 +79,30 @@ def test_pyramid_kernel_vs_oracle_large(gpu, shape, cap):
 def test_pyramid_streaming_form_equals_tiled(gpu, shape, kind):
     """k_pyr_wave (one LDS-free pass, waves of 28 output columns x 16 rows, the clip from
     per-wave partials) writes the same level as the tiled k_pyr_reduce + k_pyr_clip, bit for
-    bit, and the oracle's; 'flat' images (saturated regions) exercise the clip itself."""
+    bit, and the oracle's.  'flat' images hold saturated regions (the extremes are shared by
+    many pixels and waves); they do NOT reach the clip's rewrite branch: the oracle's clip
+    changes no value on any of these shapes (a halving map has dc = dr = 0.5, and 0.5 c + 0.5 c
+    is exact).  'plateau' images on the odd shape do (a mixed-sign pair of plateaus whose
+    resampled values round past the blurred extremes); test_gpu_setup.py covers that branch
+    in full and asserts from the oracle that it runs."""
+    _streaming_form_equals_tiled(shape, kind)
+
+
+def test_pyramid_streaming_form_equals_tiled_with_the_clip_engaged(gpu):
+    _streaming_form_equals_tiled((257, 124), 'plateau')
+
+
+def _streaming_form_equals_tiled(shape, kind):
     import _ia
     import img_preprocess as ip
     rs = np.random.RandomState(sum(shape))
     img = rs.rand(*shape)
     if kind == 'flat':
         img = np.minimum(1.0, img * 3.0)          # ~2/3 of the pixels exactly 1.0
+    elif kind == 'plateau':
+        from test_gpu_setup import assert_clip_engaged, plateau_image
+        img = plateau_image('mixed', shape)
+        assert_clip_engaged('mixed', img)
     x = dev(img)
     outs = []
     for form, oh in [(0, 0), (1, 0)]:

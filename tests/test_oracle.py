@@ -87,6 +87,49 @@ def test_pyramid_bit_exact_vs_skimage(k):
         assert np.array_equal(pyr[l], g['pyr%d_l%d' % (k, l)]), (k, l)
 
 
+def test_oracle_reproduces_reference_setup_fixture():
+    """ref_setup_golden.npz (make_setup_golden.py: the reference's pyramids of plateau and noise
+    images outside [0, 1] at 45 x 61 and 21 x 37, and its remap_luminance + compress_values +
+    pyramid chain): the oracle reproduces every array bit for bit, so it is a sound reference
+    for out-of-range data; the seeded generators still give the inputs the fixture was
+    made from."""
+    import test_gpu_setup as gs
+    g = golden('ref_setup_golden.npz')
+    images = gs.msg.golden_images()
+    assert len(images) == 16
+    for name, img in images.items():
+        assert gs.msg.sha(img) == str(g[name + '_sha']), name
+        pyr = o.compute_gaussian_pyramid(img, 3)
+        assert len(pyr) == int(g[name + '_n']) >= 3, name
+        for l in range(len(pyr) - 1):
+            assert np.array_equal(pyr[l], g['%s_l%d' % (name, l)]), (name, l)
+    A, Ap, B = gs.msg.chain_inputs()
+    assert [gs.msg.sha(x) for x in (A, Ap, B)] == [str(s) for s in g['chain_sha']]
+    Ar, Apr = o.remap_luminance(A, [Ap], B)
+    assert Apr[0].min() < -0.5 and Apr[0].max() > 1.5
+    Ac, Bc = o.compress_values(Ar, B, gs.msg.CHAIN_WEIGHT)
+    for name, img in (('A', Ac), ('Ap', Apr[0]), ('B', Bc)):
+        pyr = o.compute_gaussian_pyramid(img, 3)
+        assert len(pyr) == int(g['chain_%s_n' % name]), name
+        for l, lvl in enumerate(pyr):
+            assert np.array_equal(lvl, g['chain_%s_l%d' % (name, l)]), (name, l)
+
+
+def test_plateau_inputs_engage_the_clip():
+    """The inputs of test_gpu_setup.test_pyramid_clip_engaged_vs_oracle have teeth: on every
+    plateau pair and shape the oracle's clip changes values on the side(s) the pair can engage
+    (the fixture's sizes included), while it changes none on the saturated noise of
+    test_pyramid_streaming_form_equals_tiled[flat] nor on an even-sized plateau image."""
+    import test_gpu_setup as gs
+    assert len(gs.PLATEAU_CASES) == 18
+    for name, shape in gs.PLATEAU_CASES:
+        gs.assert_clip_engaged(name, gs.plateau_image(name, shape))
+    for shape in [(2048, 2048), (96, 130), (8, 4), (517, 300), (33, 1000), (4, 5), (2, 2), (3, 255), (257, 124)]:
+        flat = np.minimum(1.0, np.random.RandomState(sum(shape)).rand(*shape) * 3.0)
+        assert gs.clip_counts(flat) == (0, 0), shape
+    assert gs.clip_counts(gs.plateau_image('mixed', (96, 130))) == (0, 0)
+
+
 def test_initialize_Bp():
     """img_preprocess_test.py:29-42 intent, seeded."""
     img = np.random.RandomState(0xba5eba11).rand(25, 40)
