@@ -191,6 +191,9 @@ _SIGS = {
     'ia_diag_peer_trace': (ctypes.c_int, [_dp, _dp]),
     'ia_diag_screen16r': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long, _dp, _dp,
                                          _dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
+    'ia_diag_wave_rows': (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]),
+    'ia_diag_pipe_schedule': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3 + [ctypes.c_int] * 3 +
+                              [ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     'ia_diag_db3_askip': (ctypes.c_int, [_dp, ctypes.c_long, _dp]),
     'ia_diag_screen3r': (ctypes.c_int, [_dp, _dp, _dp, ctypes.c_long, _dp, ctypes.c_int, _dp, _dp, _dp]),
     'ia_diag_synth_level_shards': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs),

@@ -19,6 +19,7 @@
 #include "ia_common.h"
 #include "ia_internal.h"
 #include "ia_split16.h"
+#include "ia_pipe.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1517,7 +1518,6 @@ __global__ void k_split_best3(const Best *__restrict__ b, int M, int64_t *idx, d
     if (dist) dist[i] = b[i].d;
 }
 
-static inline int max_wave(int H, int W) { return std::min(H, (W + 2) / 3) + 1; }
 static inline int match3_blocks(long nrows) { return (int)((nrows + M3_ROWS - 1) / M3_ROWS); }
 
 // IA_COLOR16 (ia_diag_set_color16): 1 the split-f16 screen + exact stage, 0 the exhaustive
@@ -1548,7 +1548,7 @@ static inline bool c3_fuse() {
 }
 static_assert(C16_TILE >= R3_TILE, "query tiles");
 static inline size_t ws3_layout(int H, int W, long nrows, char *base, Ws3 *w) {
-    const size_t M = (size_t)max_wave(H, W), Mp = (M + 31) / 32 * 32;
+    const size_t M = (size_t)wave_max_queries(H, W), Mp = (M + 31) / 32 * 32;
     size_t o = 0;
     auto take = [&](size_t bytes) { char *p = base ? base + o : nullptr; o += align_up(bytes, 256); return p; };
     char *q3 = take(Mp * D3P * sizeof(double));
@@ -1620,19 +1620,15 @@ struct Level3 {
         dbr = reinterpret_cast<const half8 *>(a->dbr);
         sc = Scr3{w.smin, ntiles, a->nrows, w.qn, v.meta, g_c3_stats, rot ? w.nsk : nullptr,
                   rot ? db3r_meta(const_cast<void *>(a->dbr), a->nrows) : nullptr};
-        nw = (W - 1) + 3 * (H - 1) + 1;
+        nw = wave_count(H, W);
         fuse = rot && c3_fuse();
         IA_HIP(hipMemsetAsync(w.ctl, 0, 256, st));
         if (fuse) IA_HIP(hipMemsetAsync(w.dbox, 0, (size_t)H * 8 * sizeof(unsigned long long), st));
         return IA_OK;
     }
-    static void rows(int H, int W, int t, int &y_lo, int &M) {
-        y_lo = std::max(0, (t - (W - 1) + 2) / 3);
-        M = std::min(H - 1, t / 3) - y_lo + 1;
-    }
     int wave(int t, hipStream_t st) {
         int y_lo, M;
-        rows(H, W, t, y_lo, M);
+        wave_rows(H, W, t, y_lo, M);
         if (M <= 0) return IA_OK;
         f.t = t;
         f.y_lo = y_lo;
@@ -1649,7 +1645,7 @@ struct Level3 {
                                                               q3s[0], qns[0], nsks[0], q16s[0]);
             k_screen3r<<<grid, 256, 0, st>>>(dbr, ntiles, q16s[b], M, tpw, w.smin);
             int y_lo_n = 0, M_n = 0;
-            if (t + 1 < nw) rows(H, W, t + 1, y_lo_n, M_n);
+            if (t + 1 < nw) wave_rows(H, W, t + 1, y_lo_n, M_n);
             const Nx3 nx{Bsm, Blg, Bpsm, Bplg, M, y_lo_n, M_n, H, v.meta, a->rot, q3s[b ^ 1], qns[b ^ 1],
                          nsks[b ^ 1], q16s[b ^ 1], w.ctl, w.ctl + C3_CTL_ERR, w.dbox};
             Fin3 fb = f;
@@ -1683,84 +1679,8 @@ struct Level3 {
         IA_LAUNCH_CHECK("ia_synth_level3 wave");
         return IA_OK;
     }
+    int done(hipStream_t) { return IA_OK; }
 };
-
-// the coarse waves wave t of level a reads (ia_synth.hip coarse_need: the 3x3 coarse window
-// of pixel (y, x) reaches (y/2 + 1, x/2 + 1), clamped to the coarse level)
-static int c3_need(const IaSynthArgs &a, int t) {
-    int y_lo, M;
-    Level3::rows(a.H, a.W, t, y_lo, M);
-    int need = 0;
-    for (int y = y_lo; y < y_lo + M; ++y) {
-        const int x = t - 3 * y;
-        const int cy = std::min(y / 2 + 1, a.B_hs - 1), cx = std::min(x / 2 + 1, a.B_ws - 1);
-        need = std::max(need, cx + 3 * cy);
-    }
-    return need;
-}
-// 8 against 4 at the c3 size, same box, A/B/A/B: 112.6 / 111.0 vs 113.8 / 112.6 ms per
-// step, same checksum (profiles/r06_pipe_block_ab.txt)
-#ifndef IA_C3_PIPE_BLOCK
-#define IA_C3_PIPE_BLOCK 8
-#endif
-constexpr int C3_PIPE_BLOCK = IA_C3_PIPE_BLOCK;   // waves per recorded event (build-time)
-
-struct Pipe3 {   // per host thread: the level streams and events of ia_synth_levels3
-    std::vector<hipStream_t> hi;   // levels 0 .. n-2 of a call (the coarser ones): high priority
-    hipStream_t plain = nullptr;   // level n-1 (the finest): plain priority
-    std::vector<hipEvent_t> events;
-    size_t next = 0;
-    hipEvent_t last = nullptr;     // the previous call's end (IA_PIPE_DRAIN, ia_synth.hip)
-    bool last_rec = false;
-    // the streams of an n-level call: the pools grow as needed, and the finest level always
-    // takes the plain stream whatever n the first call had
-    hipError_t streams(int n, std::vector<hipStream_t> &out) {
-        hipError_t r = hipSuccess;
-        int lo = 0, pr = 0;
-        if ((r = hipDeviceGetStreamPriorityRange(&lo, &pr)) != hipSuccess) return r;
-        while ((int)hi.size() < n - 1) {
-            hipStream_t s;
-            if ((r = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, pr)) != hipSuccess) return r;
-            hi.push_back(s);
-        }
-        if (!plain && (r = hipStreamCreateWithFlags(&plain, hipStreamNonBlocking)) != hipSuccess) return r;
-        out.assign(hi.begin(), hi.begin() + (n - 1));
-        out.push_back(plain);
-        return r;
-    }
-    hipError_t release() {
-        hipError_t r = hipSuccess;
-        for (hipStream_t s : hi)
-            if (r == hipSuccess) r = hipStreamDestroy(s);
-        if (plain && r == hipSuccess) r = hipStreamDestroy(plain);
-        for (hipEvent_t e : events)
-            if (r == hipSuccess) r = hipEventDestroy(e);
-        if (last && r == hipSuccess) r = hipEventDestroy(last);
-        last = nullptr;
-        last_rec = false;
-        hi.clear();
-        plain = nullptr;
-        events.clear();
-        next = 0;
-        return r;
-    }
-    hipError_t event(hipEvent_t *e) {
-        if (next == events.size()) {
-            hipEvent_t x;
-            hipError_t r = hipEventCreateWithFlags(&x, hipEventDisableTiming);
-            if (r != hipSuccess) return r;
-            events.push_back(x);
-        }
-        *e = events[next++];
-        return hipSuccess;
-    }
-};
-static thread_local Pipe3 g_pipe3;
-// ia_release_thread_resources (ia_synth.hip): this thread's colour pipeline streams and events
-int release_pipe3() {
-    IA_HIP(g_pipe3.release());
-    return IA_OK;
-}
 
 }  // namespace ia
 
@@ -1891,22 +1811,14 @@ int ia_diag_db3_askip(const void *dbr, long nrows, float *out) {
 }
 
 int ia_synth3_status(const IaSynthArgs *levels, int n, void *stream) {
-    IA_ARG(levels && n >= 1, "ia_synth3_status: bad args");
-    IA_HIP(hipStreamSynchronize(S(stream)));
-    for (int j = 0; j < n; ++j) {
-        const IaSynthArgs &a = levels[j];
-        IA_ARG(a.workspace && a.H > 0 && a.W > 0 && a.nrows > 0, "ia_synth3_status: bad level");
-        Ws3 w{};
-        ws3_layout(a.H, a.W, a.nrows, reinterpret_cast<char *>(a.workspace), &w);
-        unsigned e = 0;
-        IA_HIP(hipMemcpy(&e, w.ctl + C3_CTL_ERR, sizeof(e), hipMemcpyDeviceToHost));
-        if (e) {
-            set_error("ia_synth3_status: a wait for a neighbouring pixel's decision timed out "
-                      "(device schedule fault)");
-            return IA_E_SCHED;
-        }
-    }
-    return IA_OK;
+    return levels_status(
+        "ia_synth3_status", levels, n, stream,
+        [](const IaSynthArgs &a) {
+            Ws3 w{};
+            ws3_layout(a.H, a.W, a.nrows, reinterpret_cast<char *>(a.workspace), &w);
+            return w.ctl + C3_CTL_ERR;
+        },
+        [](const IaSynthArgs &) { return IA_OK; });
 }
 
 int ia_synth_level3(const IaSynthArgs *a, void *stream) {
@@ -1919,9 +1831,10 @@ int ia_synth_level3(const IaSynthArgs *a, void *stream) {
     return IA_OK;
 }
 
-/* n consecutive 3-channel levels, pipelined as ia_synth_levels (ia_synth.hip): one stream per
- * level (the coarser ones at high priority), level j's wave t launched behind an event of
- * level j - 1 covering the coarse waves its pixels read (c3_need). */
+/* n consecutive 3-channel levels through the level pipeline of ia_synth_levels (ia_pipe.h),
+ * every level enqueued whole, coarse to fine (order 1): a level's waits name events already
+ * recorded.  Finest-first as the luminance path (IA_PIPE_ORDER 0) is a speed change yet to be
+ * measured here. */
 int ia_synth_levels3(const IaSynthArgs *levels, int n, void *stream) {
     IA_ARG(levels && n >= 1 && n <= 64, "ia_synth_levels3: bad level count");
     for (int j = 1; j < n; ++j)
@@ -1929,59 +1842,16 @@ int ia_synth_levels3(const IaSynthArgs *levels, int n, void *stream) {
                    levels[j].B_ws == levels[j - 1].W,
                "ia_synth_levels3: levels must be consecutive (level j's coarse B' = level j-1's B')");
     hipStream_t st = S(stream);
-    Pipe3 &P = g_pipe3;
-    // the previous call of this thread ends first (IA_PIPE_DRAIN, default 1: packets queued
-    // in the high-priority streams behind a running call slow its finest level, ia_synth.hip)
-    static const int drain = env_int("IA_PIPE_DRAIN", 1);
-    if (drain && P.last_rec) IA_HIP(hipEventSynchronize(P.last));
-    std::vector<hipStream_t> ss;   // ss[j] runs level j: high priority but the finest
-    IA_HIP(P.streams(n, ss));
-    P.next = 0;
-    hipEvent_t start;
-    IA_HIP(P.event(&start));
-    IA_HIP(hipEventRecord(start, st));
+    int rc = g_pipe.begin(n, st);
+    if (rc) return rc;
     std::vector<Level3> run(n);
-    std::vector<std::vector<hipEvent_t>> blk(n);   // blk[j][b]: level j done through block b
+    std::vector<PipeLevel> pl(n);
     for (int j = 0; j < n; ++j) {
-        IA_HIP(hipStreamWaitEvent(ss[j], start, 0));   // (init's memsets too: after the caller's work)
-        int rc = run[j].init(&levels[j], ss[j]);
-        if (rc) return rc;
-        blk[j].assign((run[j].nw + C3_PIPE_BLOCK - 1) / C3_PIPE_BLOCK, nullptr);
+        if ((rc = g_pipe.level_begin(j)) || (rc = run[j].init(&levels[j], g_pipe.stream(j)))) return rc;
+        // (the fused tail's launch of wave t also builds wave t + 1's query rows)
+        pl[j] = PipeLevel{run[j].H, run[j].W, run[j].fuse, false};
     }
-    // every level whole, coarse to fine: a level's waits name events already recorded
-    for (int j = 0; j < n; ++j) {
-        hipStream_t sj = ss[j];
-        int waited = -1;
-        for (int t = 0; t < run[j].nw; ++t) {
-            if (j > 0) {
-                // (the fused tail's launch of wave t also builds wave t + 1's query rows)
-                const int w = c3_need(levels[j], run[j].fuse && t + 1 < run[j].nw ? t + 1 : t);
-                if (w > waited) {
-                    const int b = w / C3_PIPE_BLOCK;
-                    IA_HIP(hipStreamWaitEvent(sj, blk[j - 1][b], 0));
-                    waited = b * C3_PIPE_BLOCK + C3_PIPE_BLOCK - 1;
-                }
-            }
-            int rc = run[j].wave(t, sj);
-            if (rc) return rc;
-            if ((t + 1) % C3_PIPE_BLOCK == 0 || t == run[j].nw - 1) {
-                hipEvent_t e;
-                IA_HIP(P.event(&e));
-                IA_HIP(hipEventRecord(e, sj));
-                blk[j][t / C3_PIPE_BLOCK] = e;
-            }
-        }
-    }
-    for (int j = 0; j < n; ++j) {
-        hipEvent_t e;
-        IA_HIP(P.event(&e));
-        IA_HIP(hipEventRecord(e, ss[j]));
-        IA_HIP(hipStreamWaitEvent(st, e, 0));
-    }
-    if (!P.last) IA_HIP(hipEventCreateWithFlags(&P.last, hipEventDisableTiming));
-    IA_HIP(hipEventRecord(P.last, st));
-    P.last_rec = true;
-    return IA_OK;
+    return pipe_execute(run, pl, 1, 0, st);
 }
 
 int ia_diag_screen3(const void *db3, long nrows, const double *q165, int M, double *e, double *eps,

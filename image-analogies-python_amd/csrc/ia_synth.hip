@@ -18,11 +18,11 @@
 #include "ia_finish.h"
 #include "ia_split16.h"
 #include "ia_rot16.h"
+#include "ia_pipe.h"
 #include "../../include/ia_diag.h"
 
 #include <cstdio>
 #include <cstdlib>
-#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -190,11 +190,6 @@ struct SynthWs {
 };
 constexpr int XW_CTL_ERR = 2;
 
-static inline int wave_max_queries(int H, int W) {
-    const int byw = (W + 2) / 3;   // ceil(W/3)
-    return (H < byw ? H : byw) + 1;
-}
-
 static size_t carve(SynthWs *ws, char *base, int H, int W, long nrows, int nranks) {
     const int Mmax = wave_max_queries(H, W);
     const int qr = qrows_alloc(Mmax);
@@ -314,7 +309,6 @@ static std::atomic<int> g_graph_mode{env_int("IA_GRAPH", 0)};
 static int graph_mode() { return g_graph_mode.load(std::memory_order_relaxed); }
 
 int xwave_attributes(int form, bool rot, hipFuncAttributes *at);
-int release_pipe3();
 int screen16_attributes(bool img, hipFuncAttributes *at);
 int screen_resources_r16(hipFuncAttributes *at);
 int comm_allgather(void *comm, const void *send, void *recv, size_t bytes, hipStream_t st);
@@ -400,7 +394,7 @@ struct LevelRun {
         if (rc) return rc;
         nranks = a->comm ? comm_nranks(a->comm) : (sim ? nsim : 1);
         H = a->H; W = a->W;
-        nw = (W - 1) + 3 * (H - 1) + 1;
+        nw = wave_count(H, W);
         long rows_ws = a->nrows;
         for (int r = 0; r < nsim; ++r) rows_ws = sim[r].nrows > rows_ws ? sim[r].nrows : rows_ws;
         carve(&ws, reinterpret_cast<char *>(a->workspace), H, W, rows_ws, nranks);
@@ -440,14 +434,6 @@ struct LevelRun {
             IA_HIP(hipMemsetAsync(ws.dbox, 0, (size_t)H * 2 * sizeof(unsigned long long), st));
         }
         return IA_OK;
-    }
-
-    // wave t: pixels y in [y_lo, y_hi], x = t - 3y
-    static void wave_rows(int H, int W, int t, int &y_lo, int &M) {
-        const int lo_num = t - (W - 1);
-        y_lo = lo_num > 0 ? (lo_num + 2) / 3 : 0;
-        const int y_hi = t / 3 < H - 1 ? t / 3 : H - 1;
-        M = y_hi - y_lo + 1;
     }
 
     int wave(int t, hipStream_t sq) {
@@ -696,21 +682,7 @@ struct LevelRun {
     }
 };
 
-// ---- pipelined levels (ia_synth_levels) ---------------------------------------------
-// Level l's wave t reads the coarse level l-1 only through the 3x3 coarse windows of its
-// pixels: coarse pixels up to (y/2 + 1, x/2 + 1), i.e. coarse waves <= need(t) =
-// max over the wave's pixels of min(x/2 + 1, W'-1) + 3 min(y/2 + 1, H'-1) (the mirror at
-// the coarse level's far edges stays inside that box).  So level l may start as soon as
-// level l-1 has finished need(0) and run concurrently behind it on its own stream: the
-// step's critical path becomes ~ the finest level's waves instead of the sum of all
-// levels' waves.  Levels wait on events recorded every PIPE_BLOCK waves of the level below.
-// waves per recorded event (build-time IA_PIPE_BLOCK).  8 against 4, same boxes, two
-// rounds: c1 14.73-15.07 vs 14.93-15.19, c3 69.2-70.7 vs 69.9-72.3, c4 734-743 vs 735-744
-// ms/step; 2 is slower (c1 16.1), 16 mixed (profiles/r06_pipe_block_ab.txt)
-#ifndef IA_PIPE_BLOCK
-#define IA_PIPE_BLOCK 8
-#endif
-constexpr int PIPE_BLOCK = IA_PIPE_BLOCK;
+// ---- pipelined levels (ia_synth_levels): the schedule, executor and pool of ia_pipe.h ----
 // waves a coarse level is enqueued ahead of its need (IA_PIPE_AHEAD, default 16): every
 // coarse wave enqueued before the finest level's first costs ~10 us of host time; same box,
 // two passes: c1 16.22 / 16.30 (64), 15.99 / 15.95 (32), 15.24 / 15.12 (16), 15.55 / 15.72 (8)
@@ -720,58 +692,7 @@ static int pipe_ahead() {
     return v < 0 ? 0 : v;
 }
 
-static int coarse_need(const IaSynthArgs *a, int t) {
-    int y_lo, M;
-    LevelRun::wave_rows(a->H, a->W, t, y_lo, M);
-    const int Hc = a->B_hs, Wc = a->B_ws;
-    int need = 0;
-    for (int y = y_lo; y < y_lo + M; ++y) {
-        const int x = t - 3 * y;
-        const int cy = y / 2 + 1 < Hc - 1 ? y / 2 + 1 : Hc - 1;
-        const int cx = x / 2 + 1 < Wc - 1 ? x / 2 + 1 : Wc - 1;
-        need = cx + 3 * cy > need ? cx + 3 * cy : need;
-    }
-    return need;
-}
-
-struct PipeRes {   // per host thread: the level streams and events of ia_synth_levels
-    std::vector<hipStream_t> streams;   // levels 0 .. n-2 of a call (coarser): high priority
-    hipStream_t plain = nullptr;        // level n-1 of a call (the finest): plain priority
-    std::vector<hipEvent_t> events;
-    size_t next_event = 0;
-    // pinned staging of the batch job tables: reused after the previous call's copies ran
-    void *pin = nullptr;
-    size_t pin_bytes = 0;
-    hipEvent_t staged = nullptr;
-    bool staged_rec = false;
-    hipEvent_t last = nullptr;          // the previous call's end (on its caller's stream)
-    bool last_rec = false;
-    hipError_t staging(size_t bytes, void **p) {
-        hipError_t r = hipSuccess;
-        if (!staged && (r = hipEventCreateWithFlags(&staged, hipEventDisableTiming)) != hipSuccess) return r;
-        if (staged_rec && (r = hipEventSynchronize(staged)) != hipSuccess) return r;
-        if (bytes > pin_bytes) {
-            if (pin && (r = hipHostFree(pin)) != hipSuccess) return r;
-            pin = nullptr;
-            if ((r = hipHostMalloc(&pin, bytes, hipHostMallocDefault)) != hipSuccess) return r;
-            pin_bytes = bytes;
-        }
-        staged_rec = true;
-        *p = pin;
-        return r;
-    }
-    hipError_t event(hipEvent_t *e) {
-        if (next_event == events.size()) {
-            hipEvent_t x;
-            hipError_t r = hipEventCreateWithFlags(&x, hipEventDisableTiming);
-            if (r != hipSuccess) return r;
-            events.push_back(x);
-        }
-        *e = events[next_event++];
-        return hipSuccess;
-    }
-};
-static thread_local PipeRes g_pipe;
+thread_local PipeRes g_pipe;
 
 }  // namespace ia
 
@@ -785,6 +706,39 @@ int ia_diag_xwave_trace(unsigned long long *out) {
     IA_HIP(hipMemcpy(out, g_xw_trace, (size_t)XW_TRACE_T * XW_TRACE_PX * XW_TRACE_N * 8,
                      hipMemcpyDeviceToHost));
     return IA_OK;
+}
+
+int ia_diag_wave_rows(int H, int W, int t, int Hc, int Wc, int *out) {
+    IA_ARG(out && H > 0 && W > 0 && t >= 0 && t < wave_count(H, W), "ia_diag_wave_rows: bad args");
+    wave_rows(H, W, t, out[0], out[1]);
+    out[2] = wave_count(H, W);
+    out[3] = wave_max_queries(H, W);
+    out[4] = Hc > 0 && Wc > 0 ? coarse_need(H, W, Hc, Wc, t) : -1;
+    return IA_OK;
+}
+
+int ia_diag_pipe_schedule(const int *shapes, const int *builds_next, const int *serial, int n, int order,
+                          int ahead, int *out, int cap) {
+    IA_ARG(shapes && builds_next && serial && n >= 1 && n <= 64 && ahead >= 0 && (out || cap == 0),
+           "ia_diag_pipe_schedule: bad args");
+    std::vector<PipeLevel> lv(n);
+    for (int j = 0; j < n; ++j) {
+        IA_ARG(shapes[2 * j] > 0 && shapes[2 * j + 1] > 0, "ia_diag_pipe_schedule: bad shape");
+        lv[j] = PipeLevel{shapes[2 * j], shapes[2 * j + 1], builds_next[j] != 0, serial[j] != 0};
+    }
+    struct Log {
+        int *out, cap, len;
+        int put(int kind, int j, int a, int b) {
+            if (len < cap) { int *o = out + 4 * len; o[0] = kind; o[1] = j; o[2] = a; o[3] = b; }
+            ++len;
+            return IA_OK;
+        }
+        int wave(int j, int t) { return put(0, j, t, 0); }
+        int record(int j, int b) { return put(1, j, b, 0); }
+        int wait(int j, int i, int b) { return put(2, j, i, b); }
+    } log{out, cap, 0};
+    const int rc = PipeSched<Log>(lv, ahead, log).run(order);
+    return rc ? rc : log.len;
 }
 
 int ia_diag_set_xwave(int on) {
@@ -824,26 +778,14 @@ int ia_level_resources(const IaSynthArgs *a, int *out) {
 }
 
 int ia_synth_status(const IaSynthArgs *levels, int n, void *stream) {
-    IA_ARG(levels && n >= 1, "ia_synth_status: bad args");
-    IA_HIP(hipStreamSynchronize(S(stream)));
-    for (int j = 0; j < n; ++j) {
-        const IaSynthArgs &a = levels[j];
-        IA_ARG(a.workspace && a.H > 0 && a.W > 0 && a.nrows > 0, "ia_synth_status: bad level");
-        SynthWs w;
-        carve(&w, reinterpret_cast<char *>(a.workspace), a.H, a.W, a.nrows, comm_nranks(a.comm));
-        unsigned int e = 0;
-        IA_HIP(hipMemcpy(&e, w.ctl + XW_CTL_ERR, sizeof(e), hipMemcpyDeviceToHost));
-        if (e) {
-            set_error("ia_synth_status: a wait for a neighbouring pixel's decision timed out "
-                      "(device schedule fault)");
-            return IA_E_SCHED;
-        }
-        if (comm_peer_mcap(a.comm) > 0) {
-            const int rc = ia_peer_status(a.comm);
-            if (rc) return rc;
-        }
-    }
-    return IA_OK;
+    return levels_status(
+        "ia_synth_status", levels, n, stream,
+        [](const IaSynthArgs &a) {
+            SynthWs w;
+            carve(&w, reinterpret_cast<char *>(a.workspace), a.H, a.W, a.nrows, comm_nranks(a.comm));
+            return w.ctl + XW_CTL_ERR;
+        },
+        [](const IaSynthArgs &a) { return comm_peer_mcap(a.comm) > 0 ? ia_peer_status(a.comm) : IA_OK; });
 }
 
 int ia_sched_status(int clear) {
@@ -871,26 +813,10 @@ int ia_diag_set_graph_mode(int mode) {
 int ia_release_thread_resources(void) {
     IA_HIP(g_graphs.retire());
     IA_HIP(hipDeviceSynchronize());
-    for (hipStream_t s : g_pipe.streams) IA_HIP(hipStreamDestroy(s));
-    if (g_pipe.plain) IA_HIP(hipStreamDestroy(g_pipe.plain));
-    g_pipe.plain = nullptr;
-    for (hipEvent_t e : g_pipe.events) IA_HIP(hipEventDestroy(e));
-    g_pipe.streams.clear();
     {
-        const int rc = release_pipe3();
+        const int rc = g_pipe.release();
         if (rc) return rc;
     }
-    g_pipe.events.clear();
-    if (g_pipe.pin) IA_HIP(hipHostFree(g_pipe.pin));
-    if (g_pipe.staged) IA_HIP(hipEventDestroy(g_pipe.staged));
-    g_pipe.pin = nullptr;
-    g_pipe.pin_bytes = 0;
-    g_pipe.staged = nullptr;
-    g_pipe.staged_rec = false;
-    if (g_pipe.last) IA_HIP(hipEventDestroy(g_pipe.last));
-    g_pipe.last = nullptr;
-    g_pipe.last_rec = false;
-    g_pipe.next_event = 0;
     if (g_graphs.cap) { IA_HIP(hipStreamDestroy(g_graphs.cap)); g_graphs.cap = nullptr; }
     if (g_graphs.done) { IA_HIP(hipEventDestroy(g_graphs.done)); g_graphs.done = nullptr; }
     return IA_OK;
@@ -1047,59 +973,14 @@ static int synth_levels(const IaSynthArgs *levels, int n, int K, void *stream) {
                        levels[(size_t)j * K + k].B_ws == levels[(size_t)(j - 1) * K + k].W,
                    "ia_synth_levels: levels must be consecutive (level j's coarse B' = level j-1's B')");
     hipStream_t st = S(stream);
-    // one stream per level; coarser levels at high priority (IA_PIPE_PRIO, default 1) so
-    // that they run ahead of the finest level instead of time-sharing with it.  Measured
-    // (c4, one box, `tools/gpu.sh abknob`): one level at a time 1706-1713 ms/step; pipelined
-    // with the coarse levels enqueued whole first at high priority 1641-1643 ms (the finest
-    // level's plateau screens undisturbed: k_screen16<11> 400 vs 396 us); enqueued just
-    // ahead of their need 1619-1621 ms but the plateau screens contended (414 us)
-    static const int prio_on = env_int("IA_PIPE_PRIO", 1);
-    // a call waits on the host for this thread's previous call to end (IA_PIPE_DRAIN,
-    // default 1) before it enqueues anything.  Queued behind a running call, the coarse
-    // levels' first packets (their waits on `start`) sit in the high-priority queues for the
-    // whole of the previous call's finest level, and while they do the finest level's
-    // launches run ~4x slower (c1 with no host sync between steps: 61 vs 15 ms/step, screens
-    // 39 vs 9.4 us; IA_PIPE_PRIO=0 18 ms; profiles/r06_pipe_drain_ab.txt).  The host's other
-    // per-call work (the level indexes) still overlaps the previous call
-    static const int drain = env_int("IA_PIPE_DRAIN", 1);
-    if (drain && g_pipe.last_rec) IA_HIP(hipEventSynchronize(g_pipe.last));
-    // the pools grow as needed; the finest level always takes the plain-priority stream,
-    // whatever n the first call had (a pool sized by a smaller first call used to hand a
-    // later call's coarse level a plain stream and its finest a high-priority one)
-    while ((int)g_pipe.streams.size() < n - 1) {
-        int lo = 0, hi = 0;
-        IA_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        hipStream_t s;
-        if (prio_on)
-            IA_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, hi));
-        else
-            IA_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        (void)lo;
-        g_pipe.streams.push_back(s);
-    }
-    if (!g_pipe.plain) IA_HIP(hipStreamCreateWithFlags(&g_pipe.plain, hipStreamNonBlocking));
-    auto level_stream = [&](int j) { return j == n - 1 ? g_pipe.plain : g_pipe.streams[j]; };
-    g_pipe.next_event = 0;
-    hipEvent_t start;
-    IA_HIP(g_pipe.event(&start));
-    IA_HIP(hipEventRecord(start, st));
+    int rc = g_pipe.begin(n, st);
+    if (rc) return rc;
     // the batch job tables go through a pinned host buffer kept by this thread (reused once
     // the previous call's copies have run)
     XJob *pinned = nullptr;
     if (K > 1) {
         IA_HIP(g_pipe.staging((size_t)n * K * sizeof(XJob), reinterpret_cast<void **>(&pinned)));
     }
-    std::vector<LevelRun> run(n);
-    std::vector<std::vector<hipEvent_t>> blk(n);   // blk[j][b]: level j done through block b
-    std::vector<int> next(n, 0), waited(n, -1), need_max(n, 0);
-    for (int j = 0; j < n; ++j) {
-        hipStream_t sj = level_stream(j);
-        IA_HIP(hipStreamWaitEvent(sj, start, 0));
-        int rc = run[j].init_batch(&levels[(size_t)j * K], K, sj, pinned + (size_t)j * K);
-        if (rc) return rc;
-        blk[j].assign((run[j].nw + PIPE_BLOCK - 1) / PIPE_BLOCK, nullptr);
-    }
-    // enqueue level j through wave `target` (and the coarse waves it needs, first)
     // Levels whose DB is sharded over several ranks and exchanged over RCCL never overlap
     // one another: each one's first wave waits for the previous such level's last.  RCCL's
     // kernels wait in-kernel for the other ranks, and two communicators in flight on
@@ -1120,46 +1001,15 @@ static int synth_levels(const IaSynthArgs *levels, int n, int K, void *stream) {
         if (lv(j).comm == nullptr || lv(j).nrows >= lv(j).N_total) return false;
         return !(overlap && comm_peer_mcap(lv(j).comm) > 0);
     };
-    std::function<int(int, int)> advance;
-    advance = [&](int j, int target) -> int {
-        hipStream_t sj = level_stream(j);
-        if (target > run[j].nw - 1) target = run[j].nw - 1;
-        if (next[j] == 0 && target >= 0 && multi_rank(j)) {
-            for (int i = j - 1; i >= 0; --i) {
-                if (!multi_rank(i)) continue;
-                int rc = advance(i, run[i].nw - 1);
-                if (rc) return rc;
-                IA_HIP(hipStreamWaitEvent(sj, blk[i].back(), 0));
-                break;
-            }
-        }
-        while (next[j] <= target) {
-            const int t = next[j];
-            if (j > 0) {
-                // on the fused path wave t's launch also builds wave t + 1's query rows
-                int w = coarse_need(&lv(j), run[j].xw && t + 1 < run[j].nw ? t + 1 : t);
-                need_max[j] = w > need_max[j] ? w : need_max[j];
-                w = need_max[j];
-                if (w > waited[j]) {
-                    const int b = w / PIPE_BLOCK;
-                    int rc = advance(j - 1, b * PIPE_BLOCK + PIPE_BLOCK - 1 + pipe_ahead());
-                    if (rc) return rc;
-                    IA_HIP(hipStreamWaitEvent(sj, blk[j - 1][b], 0));
-                    waited[j] = b * PIPE_BLOCK + PIPE_BLOCK - 1;
-                }
-            }
-            int rc = run[j].wave(t, sj);
-            if (rc) return rc;
-            if ((t + 1) % PIPE_BLOCK == 0 || t == run[j].nw - 1) {
-                hipEvent_t e;
-                IA_HIP(g_pipe.event(&e));
-                IA_HIP(hipEventRecord(e, sj));
-                blk[j][t / PIPE_BLOCK] = e;
-            }
-            ++next[j];
-        }
-        return IA_OK;
-    };
+    std::vector<LevelRun> run(n);
+    std::vector<PipeLevel> pl(n);
+    for (int j = 0; j < n; ++j) {
+        if ((rc = g_pipe.level_begin(j)) ||
+            (rc = run[j].init_batch(&levels[(size_t)j * K], K, g_pipe.stream(j), pinned + (size_t)j * K)))
+            return rc;
+        // (on the fused path wave t's launch also builds wave t + 1's query rows)
+        pl[j] = PipeLevel{run[j].H, run[j].W, run[j].xw, multi_rank(j)};
+    }
     // enqueue order (IA_PIPE_ORDER): 0 [default] the finest level first, coarse waves just
     // ahead of their need; 1 every level whole, coarse to fine.  One host thread enqueues
     // ~10 us of launches per wave, so with 1 the finest level's first wave was enqueued only
@@ -1167,25 +1017,7 @@ static int synth_levels(const IaSynthArgs *levels, int n, int K, void *stream) {
     // Same box, round 6: c1 18.51 -> 16.30, c3 76.0 -> 71.3, c4 783.7 -> 750.8, c5 794 -> 786
     // ms/step (profiles/r06_pipe_order_ab.txt)
     static const int order = env_int("IA_PIPE_ORDER", 0);
-    for (int i = 0; i < n; ++i) {
-        const int j = order ? i : n - 1 - i;
-        int rc = advance(j, run[j].nw - 1);
-        if (rc) return rc;
-    }
-    for (int j = 0; j < n; ++j) {
-        hipStream_t sj = level_stream(j);
-        int rc = run[j].done(sj);
-        if (rc) return rc;
-        hipEvent_t e;
-        IA_HIP(g_pipe.event(&e));
-        IA_HIP(hipEventRecord(e, sj));
-        IA_HIP(hipStreamWaitEvent(st, e, 0));
-    }
-    if (pinned) IA_HIP(hipEventRecord(g_pipe.staged, st));
-    if (!g_pipe.last) IA_HIP(hipEventCreateWithFlags(&g_pipe.last, hipEventDisableTiming));
-    IA_HIP(hipEventRecord(g_pipe.last, st));
-    g_pipe.last_rec = true;
-    return IA_OK;
+    return pipe_execute(run, pl, order, pipe_ahead(), st);
 }
 
 int ia_synth_levels(const IaSynthArgs *levels, int n, void *stream) { return synth_levels(levels, n, 1, stream); }

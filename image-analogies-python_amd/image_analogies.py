@@ -128,6 +128,16 @@ def synthesize_levels_dev(calls):
     return [c.result() for c in calls]
 
 
+def level_runs(levels):
+    """Slices (i, j) of the ascending list `levels` that hold consecutive levels: each run
+    goes through one pipelined call."""
+    i = 0
+    for j in range(1, len(levels) + 1):
+        if j == len(levels) or levels[j] != levels[j - 1] + 1:
+            yield i, j
+            i = j
+
+
 def wave_max_queries(H, W):
     """Most pixels of one wave of an H x W level (t = x + 3y), + 1 as ia_synth.hip's."""
     return min(H, (W + 2) // 3) + 1
@@ -282,15 +292,9 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
         out[level] = (s, im) if dbg is None else (s, im, dbg)
     if args:
         # consecutive runs of levels go through one pipelined call each
-        lv = sorted(out)
-        i = 0
-        while i < len(args):
-            j = i + 1
-            while j < len(args) and lv[j] == lv[j - 1] + 1:
-                j += 1
+        for i, j in level_runs(sorted(out)):
             arr = (_ia.IaSynthArgs * (j - i))(*args[i:j])
             _ia.check(lib.ia_synth_levels3(arr, j - i, st), 'ia_synth_levels3')
-            i = j
         # the level streams are joined into st: buffers freed after this return are reused
         # only by work queued on st behind that join (the caching allocator's stream order)
         del keep
@@ -381,15 +385,10 @@ def synthesize_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights,
             print('[ia] level %d/%d done %.3f s' % (level, max_levels - 1, time.time() - t_start),
                   file=sys.stderr, flush=True)
     # runs of consecutive levels go to ia_synth_levels together
-    i = 0
-    while i < len(calls):
-        j = i + 1
-        while j < len(calls) and calls[j][0] == calls[j - 1][0] + 1:
-            j += 1
+    for i, j in level_runs([level for level, _ in calls]):
         res = synthesize_levels_dev([c for _, c in calls[i:j]])
         for (level, _), r in zip(calls[i:j], res):
             out[level] = r
-        i = j
     done += [c for _, c in calls]
     if check and done:
         # waits inside the device schedule (a neighbour's decision, another rank's records)

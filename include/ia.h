@@ -370,7 +370,8 @@ int ia_prof_launches(int rec, float *ms, int *M, int max);
  * tail_ms[i] = end of screen i -> end of its exact-stage / fused kernel, gap_ms[i] = that
  * -> the start of screen i + 1 on the level's stream (0 for the last wave) */
 int ia_prof_waves(int rec, float *tail_ms, float *gap_ms, int max);
-/* destroy the calling host thread's graph-capture stream and last executable graph */
+/* destroy the calling host thread's graph-capture stream and last executable graph, and its
+ * level-pipeline pool (the streams and events ia_synth_levels and ia_synth_levels3 share) */
 int ia_release_thread_resources(void);
 
 /* ---- multi-GPU: RCCL communicator over xGMI, one process per GPU. */

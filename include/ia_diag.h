@@ -124,6 +124,21 @@ int ia_diag_peer_stress(void *comm, int nwaves, int M, int *bad, void *stream);
  * doubles) */
 int ia_diag_peer_trace(void *comm, double *out);
 
+/* the level pipeline's host logic (csrc/ia_pipe.h); neither call touches a device.
+ * ia_diag_wave_rows: wave t (pixels x + 3y = t) of an H x W level: out = {y_lo, M (rows y_lo ..
+ * y_lo + M - 1), the level's wave count, the most queries of a wave + 1 (the workspaces' size),
+ * the last wave of the coarse Hc x Wc level that wave t reads (-1 with Hc or Wc <= 0)}.
+ * ia_diag_pipe_schedule: what a pipelined call of n levels (shapes[2j], shapes[2j + 1] = H, W of
+ * level j, coarse to fine; builds_next[j]: the launch of wave t also builds wave t + 1's query
+ * rows; serial[j]: a serialised multi-rank level) enqueues, in order, for the enqueue order
+ * (IA_PIPE_ORDER) and look-ahead (IA_PIPE_AHEAD) given: 4 ints per action, {0, j, t, 0} wave t of
+ * level j, {1, j, b, 0} record "level j done through block b" (IA_PIPE_BLOCK = 8 waves),
+ * {2, j, i, b} level j waits for block b of level i.  Writes at most cap actions; returns their
+ * number (or IA_E_ARG). */
+int ia_diag_wave_rows(int H, int W, int t, int Hc, int Wc, int *out);
+int ia_diag_pipe_schedule(const int *shapes, const int *builds_next, const int *serial, int n, int order,
+                          int ahead, int *out, int cap);
+
 /* R16c (3-channel rotated screen): A_skip of a rotated DB (fp32); one screen of M given query
  * rows (M x 165) -> tile minima in unscaled units e[M][ntiles], eps[M] (the exact stage's
  * bound), qn[M] = |q'|^2 */

@@ -238,6 +238,53 @@ def test_synthesis3_vs_oracle(gpu, color16, n_ap, k, matcher, pipeline):
         assert np.array_equal(rec['coh_dist'], rd['coh_dist']), level
 
 
+def test_colour_and_luminance_calls_share_one_pipeline_pool(gpu, color16):
+    """One host thread, no ia_release_thread_resources in between: a pipelined 3-channel
+    synthesis, a pipelined luminance one with more levels (the pool of level streams grows;
+    each call's finest level takes the plain-priority stream), the 3-channel one again; then
+    the pool released and one more luminance call (streams and events made anew).  Every
+    result equals the oracle bit for bit."""
+    import _ia
+    import ia_oracle_c as oc
+    import image_analogies as ia
+    from conftest import analogy_inputs
+    color16(1)
+    A3, Ap3, B3, Bp3, L3 = inputs(84, (36, 44), (30, 34), n_ap=1)
+    w3 = o.compute_weights(3, 5, 12, 3)
+    As3 = o.create_index(A3, Ap3, L3)
+    Bp3_ref = [b.copy() for b in Bp3]
+    ref3 = {l: o.synthesize_level(l, L3, A3, Ap3, B3, Bp3_ref, As3[l], w3, 1.0) for l in range(1, L3)}
+    A, Aps, B = analogy_inputs(61, (64, 77), (60, 84), n_ap=2)
+    A1, Ap1, B1, Bp1, L1 = o.setup_luminance(A, Aps, B, seed=61)
+    w1 = o.compute_weights(3, 5, 12, 1)
+    ref1 = oc.synthesize(A1, Ap1, B1, [b.copy() for b in Bp1], L1, 1.0, w1)
+    assert L1 > L3
+
+    def colour3():
+        Bp_dev = [dev(b) for b in Bp3]
+        out = ia.synthesize_dev([dev(p) for p in A3], [[dev(p) for p in q] for q in Ap3],
+                                [dev(p) for p in B3], Bp_dev, L3, 1.0, w3, pipeline=True)
+        for l in range(1, L3):
+            assert np.array_equal(out[l][0].cpu().numpy(), ref3[l][0]), l
+            assert np.array_equal(out[l][1].cpu().numpy(), ref3[l][1]), l
+            assert np.array_equal(Bp_dev[l].cpu().numpy(), Bp3_ref[l]), l
+
+    def luminance():
+        Bp_dev = [dev(b) for b in Bp1]
+        out = ia.synthesize_dev([dev(p) for p in A1], [[dev(p) for p in q] for q in Ap1],
+                                [dev(p) for p in B1], Bp_dev, L1, 1.0, w1, pipeline=True)
+        for l in range(1, L1):
+            assert np.array_equal(out[l][0].cpu().numpy(), ref1[l][1]), l
+            assert np.array_equal(out[l][1].cpu().numpy(), ref1[l][2]), l
+            assert np.array_equal(Bp_dev[l].cpu().numpy(), ref1[l][0]), l
+
+    colour3()
+    luminance()
+    colour3()
+    _ia.check(_ia.lib().ia_release_thread_resources(), 'ia_release_thread_resources')
+    luminance()
+
+
 def test_synthesis3_split_larger_vs_oracle(gpu, color16):
     """A larger 3-channel synthesis on the split-f16 screen (A 72 x 90, two A' images, B
     60 x 66, every level): s, im and B' equal the oracle's, and the exact stage's work stays

@@ -66,12 +66,42 @@ def test_num_layers_and_index_maps():
 
 # ---- skewed wavefront t = x + 3y ---------------------------------------------------------------
 
-def wave_rows(t, H, W):
-    """y range of wave t — the formula of ia_synth_level's loop (ia_synth.hip)."""
+def wave_rows_restated(t, H, W):
+    """y range of wave t — the formula of csrc/ia_pipe.h wave_rows, restated (a cross-check of
+    the library's only: test_library_wave_geometry_equals_its_restatement)."""
     lo_num = t - (W - 1)
     y_lo = (lo_num + 2) // 3 if lo_num > 0 else 0
     y_hi = min(t // 3, H - 1)
     return y_lo, y_hi
+
+
+def lib_wave(t, H, W, Hc=0, Wc=0):
+    """ia_diag_wave_rows: [y_lo, M, wave count, most queries of a wave + 1, coarse need]."""
+    import _ia
+    out = (ctypes.c_int * 5)()
+    assert _ia.lib().ia_diag_wave_rows(H, W, t, Hc, Wc, out) == 0, _ia.last_error()
+    return list(out)
+
+
+def wave_rows(t, H, W):
+    """y range of wave t as the library's level loops take it."""
+    y_lo, M = lib_wave(t, H, W)[:2]
+    return y_lo, y_lo + M - 1
+
+
+def test_library_wave_geometry_equals_its_restatement():
+    import image_analogies as ia
+    for H in range(1, 20):
+        for W in range(1, 25):
+            nw = (W - 1) + 3 * (H - 1) + 1
+            most = 0
+            for t in range(nw):
+                y_lo, M, n, mq, need = lib_wave(t, H, W)
+                assert (y_lo, y_lo + M - 1) == wave_rows_restated(t, H, W)
+                assert n == nw and need == -1
+                assert mq == ia.wave_max_queries(H, W)
+                most = max(most, M)
+            assert most <= mq - 1           # (the + 1 of the workspaces' size)
 
 
 def read_set(y, x, H, W):
@@ -156,6 +186,129 @@ def test_wavefront_synthesis_equals_scanline_oracle():
                 im[y * W + x] = i
         assert np.array_equal(Bp_w[level], ref[level][0])
         assert np.array_equal(s, ref[level][1]) and np.array_equal(im, ref[level][2])
+
+
+# ---- the level pipeline's schedule (csrc/ia_pipe.h) ---------------------------------------------
+
+PIPE_BLOCK = 8
+
+
+def coarse_read(t, H, W):
+    """The last coarse wave that wave t of an H x W level reads, by the definition: the largest
+    cx + 3 cy over the 3 x 3 coarse windows (centre (y >> 1, x >> 1), reflected) of its pixels."""
+    Hc, Wc = (H + 1) // 2, (W + 1) // 2
+    need = -1
+    for y in range(H):
+        x = t - 3 * y
+        if 0 <= x < W:
+            for dy in (-1, 0, 1):
+                for dx in (-1, 0, 1):
+                    need = max(need, int(o.sym_index((x >> 1) + dx, Wc)) + 3 * int(o.sym_index((y >> 1) + dy, Hc)))
+    return need
+
+
+_coarse_read = {}
+
+
+def coarse_read_all(H, W):
+    if (H, W) not in _coarse_read:
+        _coarse_read[H, W] = [coarse_read(t, H, W) for t in range((W - 1) + 3 * (H - 1) + 1)]
+    return _coarse_read[H, W]
+
+
+def test_coarse_need_is_the_last_coarse_wave_read():
+    """coarse_need (what a wave waits for) against the coarse windows its pixels read: >= is
+    the soundness condition; the formula is in fact tight (the reflected far edge maps n to
+    n - 1, inside the clamped box)."""
+    for H in range(1, 14):
+        for W in range(1, 18):
+            Hc, Wc = (H + 1) // 2, (W + 1) // 2
+            want = coarse_read_all(H, W)
+            got = [lib_wave(t, H, W, Hc, Wc)[4] for t in range(len(want))]
+            assert all(g >= w for g, w in zip(got, want)), (H, W)
+            # (a wave without pixels, W < 3, reads nothing: -1 here, 0 in the library)
+            assert [g for g, w in zip(got, want) if w >= 0] == [w for w in want if w >= 0], (H, W)
+
+
+def pipe_schedule(shapes, builds_next, serial, order, ahead):
+    import _ia
+    n = len(shapes)
+    ints = lambda v: (ctypes.c_int * len(v))(*[int(x) for x in v])  # noqa: E731
+    cap = sum(2 * ((W - 1) + 3 * (H - 1) + 1) + 2 for H, W in shapes) + 8
+    out = (ctypes.c_int * (4 * cap))()
+    k = _ia.lib().ia_diag_pipe_schedule(ints([v for s in shapes for v in s]), ints(builds_next), ints(serial), n,
+                                        order, ahead, out, cap)
+    assert 0 <= k <= cap, (k, _ia.last_error())
+    return [tuple(out[4 * i:4 * i + 4]) for i in range(k)]
+
+
+def check_schedule(shapes, builds_next, serial, order, acts):
+    """The properties every emitted sequence must have (see the test below)."""
+    n = len(shapes)
+    nw = [(W - 1) + 3 * (H - 1) + 1 for H, W in shapes]
+    nxt = [0] * n                          # waves of each level so far
+    recorded = [set() for _ in range(n)]
+    covered = [-1] * n                     # the coarse wave level j's waits so far cover
+    serial_waits = [set() for _ in range(n)]
+    for kind, j, a, b in acts:
+        assert 0 <= j < n
+        if kind == 0:                      # wave a of level j
+            assert a == nxt[j] and a < nw[j]
+            if j > 0:
+                reads = coarse_read_all(*shapes[j])
+                need = reads[a]
+                if builds_next[j] and a + 1 < nw[j]:
+                    need = max(need, reads[a + 1])
+                assert covered[j] >= need, (shapes, j, a)
+                if order == 1:             # every level whole, coarse to fine
+                    assert nxt[j - 1] == nw[j - 1]
+            if a == 0 and serial[j]:
+                below = [i for i in range(j) if serial[i]]
+                if below:
+                    assert (below[-1], (nw[below[-1]] - 1) // PIPE_BLOCK) in serial_waits[j]
+            nxt[j] += 1
+        elif kind == 1:                    # record block a of level j
+            assert a not in recorded[j]
+            assert nxt[j] - 1 == min((a + 1) * PIPE_BLOCK - 1, nw[j] - 1)
+            recorded[j].add(a)
+        else:                              # level j waits for block b of level a
+            assert kind == 2 and 0 <= a < n and a != j
+            assert b in recorded[a]
+            if a == j - 1:
+                covered[j] = max(covered[j], min((b + 1) * PIPE_BLOCK - 1, nw[a] - 1))
+            serial_waits[j].add((a, b))
+    assert nxt == nw
+    assert all(len(recorded[j]) == (nw[j] + PIPE_BLOCK - 1) // PIPE_BLOCK for j in range(n))
+
+
+def test_pipeline_schedule_orders_every_wave_behind_the_coarse_waves_it_reads():
+    """The shipped scheduler (ia_diag_pipe_schedule runs the PipeSched that ia_synth_levels and
+    ia_synth_levels3 execute) on chains of 2-4 levels halved from every finest shape H <= 13,
+    W <= 17, both enqueue orders, look-ahead 0 / 3 / 16, the "builds wave t + 1" flag off, on
+    and alternating: each level's waves once and in order; a block recorded right after its
+    last wave; a wait only on a recorded block; before a wave, waits covering every coarse wave
+    it (and with the flag wave t + 1) reads, by coarse_read; with order 1 each level whole
+    behind the one below.  Serialised multi-rank levels {1, 3} of 4: level 3's first wave
+    behind a wait on level 1's last block."""
+    for H in range(1, 14):
+        for W in range(1, 18):
+            for n in (2, 3, 4):
+                shapes = [(H, W)]
+                while len(shapes) < n:
+                    shapes.insert(0, ((shapes[0][0] + 1) // 2, (shapes[0][1] + 1) // 2))
+                for flags in ([0] * n, [1] * n, [j & 1 for j in range(n)]):
+                    for order in (0, 1):
+                        for ahead in (0, 3, 16):
+                            acts = pipe_schedule(shapes, flags, [0] * n, order, ahead)
+                            check_schedule(shapes, flags, [0] * n, order, acts)
+                if n == 4:
+                    serial = [0, 1, 0, 1]
+                    for order in (0, 1):
+                        acts = pipe_schedule(shapes, [1] * n, serial, order, 16)
+                        check_schedule(shapes, [1] * n, serial, order, acts)
+                        first3 = acts.index((0, 3, 0, 0))
+                        last1 = ((shapes[1][1] - 1) + 3 * (shapes[1][0] - 1)) // PIPE_BLOCK
+                        assert (2, 3, 1, last1) in acts[:first3]
 
 
 # ---- sharded database: per-rank exact winners + lexicographic min (gloo, 2 ranks) -------------
