@@ -12,12 +12,17 @@
 // ia_db3_build_rot adds the rotated split operand (R16c, 352 B per row, §4e).  Per wave: the
 // query rows (k_query3s / k_query3r), the MFMA screen's minimum per (query, 32-row tile)
 // (k_screen3: 33 MFMAs per 32x32 tile; k_screen3r: 11), then k_exact3: every row of the tiles
-// within the bound rescored in fp64 in the oracle's order, the coherence pick over the causal
-// 3x5 window, the kappa test and the B' update of all three channels, one 256-thread
-// workgroup per pixel.  IA_COLOR16=0 keeps the exhaustive fp64 search (k_match3 +
-// k_finish3w).  ia_synth_levels3 runs the levels pipelined.  Single GPU, exact matcher.
+// within the bound rescored in fp64 in the oracle's order, and the per-pixel tail, one
+// 256-thread workgroup per pixel.  On R16c levels k_exact3<true> (IA_C3_FUSE, default 1) also
+// writes the next wave's query rows, so a wave is two launches.  IA_COLOR16=0 keeps the
+// exhaustive fp64 search (k_match3) with the tail in k_finish3w.  The tail itself (coherence
+// pick over the causal 3x5 window, kappa test, s / im and the debug record) is the tail core
+// of ia_finish.h, shared with the luminance kernels (c3_window, c3_decide); the kernels here
+// add the 165-term distances and the B' store of all three channels.  ia_synth_levels3 runs
+// the levels pipelined.  Single GPU, exact matcher.
 #include "ia_common.h"
 #include "ia_internal.h"
+#include "ia_finish.h"
 #include "ia_split16.h"
 #include "ia_pipe.h"
 
@@ -840,36 +845,18 @@ __global__ __launch_bounds__(256) void k_match3(const double *__restrict__ db3, 
     }
 }
 
-__device__ __forceinline__ void best3(double &bd, long long &bi, double d, long long i) {
-    if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
-}
-
 // per query: the minimum over the blocks' partials (one block per query)
 __global__ __launch_bounds__(256) void k_reduce3(const Best *__restrict__ part, int nb,
                                                  Best *__restrict__ best) {
     __shared__ double sd[4];
     __shared__ long long si[4];
-    const Best *p = part + (long)blockIdx.x * nb;
-    double bd = INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
-    for (int i = threadIdx.x; i < nb; i += 256) best3(bd, bi, p[i].d, p[i].idx);
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(bd, o);
-        const long long oi = __shfl_xor(bi, o);
-        best3(bd, bi, od, oi);
-    }
-    if ((threadIdx.x & 63) == 0) { sd[threadIdx.x >> 6] = bd; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) best3(bd, bi, sd[w], si[w]);
-        best[blockIdx.x] = Best{bd, bi};
-    }
+    const Best b = block_best(part + (long)blockIdx.x * nb, nb, sd, si);
+    if (threadIdx.x == 0) best[blockIdx.x] = b;
 }
 
 struct Fin3 {
     const double *db3;       // rows of the level (row0 = 0: single GPU)
     const double *q3;
-    const Best *best;
     const double *Ap_lg;     // nAp x Ah x Aw x 3
     int Ah, Aw;
     int t, y_lo, W;
@@ -880,91 +867,30 @@ struct Fin3 {
     double *dbg_dist;
 };
 
-// distance of DB row ix to the query: plain (sqrt of the pairwise sum) or weighted (s*s,
-// s = sqrt(pairwise(((a - q) w)^2)), algorithms.py:133-135)
-__device__ __forceinline__ double row3_dist(const Fin3 &f, long ix, const double *q,
-                                            const double *w) {
-    const double *a = f.db3 + ix * D3P;
-    Pw165 pw;
-#pragma unroll 5
-    for (int k = 0; k < D3; ++k) {
-        const double d = w ? (a[k] - q[k]) * w[k] : a[k] - q[k];
-        pw.feed(k, d * d);
-    }
-    const double s = sqrt(pw.result());
-    return w ? s * s : s;
+// The per-pixel tail of both colour tail kernels (k_exact3, k_finish3w) on the tail core of
+// ia_finish.h.  Thread k < 15: window position k of pixel (y, x) into LDS (rix: its DB row,
+// -1 none; rpos: row, col, A' image).
+__device__ __forceinline__ void c3_window(int k, int y, int x, const Fin3 &f, long long *rix,
+                                          int (*rpos)[3]) {
+    const CohPos p = coh_pos(k, y, x, f.W, f.Ah, f.Aw, f.s, f.im);
+    rix[k] = p.row;
+    rpos[k][0] = p.r; rpos[k][1] = p.c; rpos[k][2] = p.im;
 }
-
-// the per-pixel tail (image_analogies.py:169-217 with best_coherence_match and
-// compute_distance, algorithms.py:92-135), one 64-lane wave per pixel of the wave
-__global__ __launch_bounds__(64) void k_finish3(Fin3 f) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    const int y = f.y_lo + m, x = f.t - 3 * y;
-    const int W = f.W, Ah = f.Ah, Aw = f.Aw;
-    const double *q = f.q3 + (long)m * D3P;
-    const long long app = f.best[m].idx;
-    const long hw = (long)Ah * Aw;
-    // coherence candidates: lanes 0..14 = product(rows y-2..y, cols x-2..x+2), scanline-earlier
-    double cd = INFINITY;
-    long long cl = 0x7fffffffffffffffLL;
-    long cix = -1;
-    int cr = 0, cc = 0, cim = 0;
-    const bool first = y == 0 && x == 0;
-    if (!first && lane < 15) {
-        const int rr = y - 2 + lane / 5, rc = x - 2 + lane % 5;
-        if (rr >= 0 && rc >= 0 && rc < W && (rr < y || rc < x)) {
-            const long sidx = (long)rr * W + rc;
-            const int sr = f.s[2 * sidx] + y - rr, sc = f.s[2 * sidx + 1] + x - rc;
-            if (sr >= 0 && sr < Ah && sc >= 0 && sc < Aw) {
-                const int simg = f.im[sidx];
-                cix = ((long)Ah * simg + sr) * Aw + sc;
-                cr = sr; cc = sc; cim = simg;
-                cd = row3_dist(f, cix, q, nullptr);
-                cl = lane;
-            }
-        }
-    }
-    double bd = cd;
-    long long bl = cl;
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(bd, o);
-        const long long ol = __shfl_xor(bl, o);
-        best3(bd, bl, od, ol);
-    }
-    const bool valid = bl != 0x7fffffffffffffffLL;
-    const int win = valid ? (int)bl : 0;
-    const long wix = __shfl(cix, win);
-    const int wr = __shfl(cr, win), wc = __shfl(cc, win), wim = __shfl(cim, win);
-    // the two weighted distances (lanes 0 and 1), then the kappa test and the update
-    double dw = 0.0;
-    if (valid && lane == 0) dw = row3_dist(f, app, q, f.weights);
-    if (valid && lane == 1) dw = row3_dist(f, wix, q, f.weights);
-    const double d_app = __shfl(dw, 0), d_coh = __shfl(dw, 1);
-    long img = app / hw;
-    long rem = app - img * hw;
-    const int ar = (int)(rem / Aw), ac = (int)(rem - (long)(rem / Aw) * Aw);
-    int pr = ar, pc = ac;
-    if (valid && d_coh <= d_app * f.kappa_factor) { pr = wr; pc = wc; img = wim; }
-    const long qpx = (long)y * W + x;
-    if (lane < 3)
-        f.Bp_lg[qpx * 3 + lane] = f.Ap_lg[((img * hw) + (long)pr * Aw + pc) * 3 + lane];
-    if (lane == 0) {
-        f.s[2 * qpx] = pr;
-        f.s[2 * qpx + 1] = pc;
-        f.im[qpx] = (int32_t)img;
-        if (f.dbg_px) {
-            int32_t *o = f.dbg_px + 7 * qpx;
-            o[0] = ar;
-            o[1] = ac;
-            o[2] = valid ? wr : 0;
-            o[3] = valid ? wc : 0;
-            o[4] = valid ? y - 2 + win / 5 : 0;
-            o[5] = valid ? x - 2 + win % 5 : 0;
-            o[6] = valid;
-            f.dbg_dist[2 * qpx] = valid ? d_app : 0.0;
-            f.dbg_dist[2 * qpx + 1] = valid ? d_coh : 0.0;
-        }
-    }
+// One whole wave, once the window rows' distances are in LDS (sump: sqrt of the plain sum,
+// +inf where rix < 0; sumw: weighted) and the exact winner app with its weighted distance
+// d_app is known: the coherence pick, the kappa test, s / im and the debug record.  Returns
+// the offset in Ap_lg of the chosen pixel's three channels (the B' store is the caller's).
+__device__ __forceinline__ long c3_decide(const Fin3 &f, int y, int x, int lane, long long app,
+                                          double d_app, const double *sump, const double *sumw,
+                                          const long long *rix, const int (*rpos)[3]) {
+    int win;
+    const bool valid = coh_first_min(lane < 15 ? sump[lane] : INFINITY, lane, win);
+    const CohSel c = coh_sel(CohPos{rix[win], rpos[win][0], rpos[win][1], rpos[win][2]}, win, valid,
+                             y, x, sumw[win]);
+    const long hw = (long)f.Ah * f.Aw;
+    const TailSel p = kappa_pick(app, hw, f.Aw, d_app, c, f.kappa_factor);
+    if (lane == 0) tail_record((long)y * f.W + x, p, c, d_app, f.s, f.im, f.dbg_px, f.dbg_dist);
+    return (p.img * hw + (long)p.pr * f.Aw + p.pc) * 3;
 }
 
 // the exact stage's inputs on the split-f16 screen: per (query, row tile) minima, |q'|^2
@@ -1002,7 +928,7 @@ __device__ __forceinline__ double c3_tseg(float emin, float amax0, double nqq, b
 // Pw165's accumulator j of both halves (i < 10: k < 80; 10 <= i < 20: 80 <= k < 160) and,
 // for j < 5, the tail term k = 160 + j.  All 21 loads issue before any use (one round trip),
 // the accumulators are summed in Pw165's order in registers, and the row's part 0 finishes the
-// two trees and the tail from LDS: the same value as pw165_sum / row3_dist, with no 165-term
+// two trees and the tail from LDS: the same value as pw165_sum, with no 165-term
 // serial sum and no (row, feature) term array.
 constexpr int R8_N = 21;
 struct Acc8 {
@@ -1053,7 +979,7 @@ __device__ __forceinline__ double acc8_sum(const Acc8 *acc, bool weighted) {
 // threshold; then per candidate tile its 32 rows, 8 threads each (acc8_row: plain and weighted
 // sums, so the winner's weighted distance needs no second read), with the 15 coherence rows
 // in the first tile's round trip; the lexicographic (distance, row) minimum carries its
-// weighted distance; coherence pick, kappa test and the B' update as k_finish3w.
+// weighted distance; coherence pick, kappa test and the record by c3_decide, then B'.
 // FUSE (the R16c path, IA_C3_FUSE): the same launch also writes the query rows of wave t + 1
 // (as k_query3r / r3_query; k_xwave's scheme): the workgroup of pixel (y, x)
 // builds the row of (y, x + 1).  Of its 165 features only the B' samples of two pixels can
@@ -1105,9 +1031,7 @@ __global__ __launch_bounds__(256) void k_exact3(Fin3 f, Scr3 sc, Nx3 nx) {
     }
     const int ro = tid >> 3, j = tid & 7;
     const int y = f.y_lo + m, x = f.t - 3 * y;
-    const int W = f.W, Ah = f.Ah, Aw = f.Aw;
-    const long hw = (long)Ah * Aw;
-    const bool first = y == 0 && x == 0;
+    const int W = f.W;
     const bool cur = !FUSE || m < nx.M;
     const bool nxt = FUSE && y >= nx.y_lo_n && y < nx.y_lo_n + nx.M_n;
     // FUSE: feature tid of the next query (y, x + 1): loaded now unless it is a wave-t sample
@@ -1134,24 +1058,7 @@ __global__ __launch_bounds__(256) void k_exact3(Fin3 f, Scr3 sc, Nx3 nx) {
         qs[tid] = f.q3[(long)m * D3P + tid];
         wsh[tid] = tid < D3 ? f.weights[tid] : 0.0;
     }
-    if (tid < 15) {
-        long long cix = -1;
-        int cr = 0, cc = 0, cim = 0;
-        if (!first) {
-            const int rr = y - 2 + tid / 5, rc = x - 2 + tid % 5;
-            if (rr >= 0 && rc >= 0 && rc < W && (rr < y || rc < x)) {
-                const long sidx = (long)rr * W + rc;
-                const int sr = f.s[2 * sidx] + y - rr, scc = f.s[2 * sidx + 1] + x - rc;
-                if (sr >= 0 && sr < Ah && scc >= 0 && scc < Aw) {
-                    const int simg = f.im[sidx];
-                    cix = ((long)Ah * simg + sr) * Aw + scc;
-                    cr = sr; cc = scc; cim = simg;
-                }
-            }
-        }
-        rix[tid] = cix;
-        rpos[tid][0] = cr; rpos[tid][1] = cc; rpos[tid][2] = cim;
-    }
+    if (tid < 15) c3_window(tid, y, x, f, rix, rpos);
     const int stride = c3_stride(sc.ntiles);
     const float4 *sm4 = reinterpret_cast<const float4 *>(sc.smin + (long)m * stride);
     const int n4 = stride / 4;
@@ -1261,28 +1168,10 @@ __global__ __launch_bounds__(256) void k_exact3(Fin3 f, Scr3 sc, Nx3 nx) {
 #pragma unroll
     for (int w = 1; w < 4; ++w)
         if (rd[w] < wd || (rd[w] == wd && ri[w] < wi)) { wd = rd[w]; wi = ri[w]; ww = rw[w]; }
-    const long long app = wi;
-    // coherence: the first minimum of the plain distances in (row, col) candidate order
-    double cd = lane < 15 && rix[lane] >= 0 ? sump[lane] : INFINITY;
-    long long cl = lane < 15 && rix[lane] >= 0 ? lane : 0x7fffffffffffffffLL;
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(cd, o);
-        const long long ol = __shfl_xor(cl, o);
-        best3(cd, cl, od, ol);
-    }
-    const bool valid = cl != 0x7fffffffffffffffLL;
-    const int win = valid ? (int)cl : 0;
-    const int wr = rpos[win][0], wc = rpos[win][1], wim = rpos[win][2];
-    const double d_app = valid ? ww : 0.0, d_coh = valid ? sumw[win] : 0.0;
-    long img = app / hw;
-    long rem = app - img * hw;
-    const int ar = (int)(rem / Aw), ac = (int)(rem - (long)(rem / Aw) * Aw);
-    int pr = ar, pc = ac;
-    if (valid && d_coh <= d_app * f.kappa_factor) { pr = wr; pc = wc; img = wim; }
-    const long qpx = (long)y * W + x;
+    const long src = c3_decide(f, y, x, lane, wi, ww, sump, sumw, rix, rpos);
     if (lane < 3) {
-        const double val = f.Ap_lg[((img * hw) + (long)pr * Aw + pc) * 3 + lane];
-        f.Bp_lg[qpx * 3 + lane] = val;
+        const double val = f.Ap_lg[src + lane];
+        f.Bp_lg[((long)y * W + x) * 3 + lane] = val;
         if constexpr (FUSE) {
             // the decision for the lower neighbour's next query, and this pixel's own
             ownv[lane] = val;
@@ -1291,23 +1180,6 @@ __global__ __launch_bounds__(256) void k_exact3(Fin3 f, Scr3 sc, Nx3 nx) {
             __hip_atomic_store(d, c3_gran(f.t + 1, (unsigned)bits), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(d + 1, c3_gran(f.t + 1, (unsigned)(bits >> 32)), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (lane == 0) {
-        f.s[2 * qpx] = pr;
-        f.s[2 * qpx + 1] = pc;
-        f.im[qpx] = (int32_t)img;
-        if (f.dbg_px) {
-            int32_t *o = f.dbg_px + 7 * qpx;
-            o[0] = ar;
-            o[1] = ac;
-            o[2] = valid ? wr : 0;
-            o[3] = valid ? wc : 0;
-            o[4] = valid ? y - 2 + win / 5 : 0;
-            o[5] = valid ? x - 2 + win % 5 : 0;
-            o[6] = valid;
-            f.dbg_dist[2 * qpx] = valid ? d_app : 0.0;
-            f.dbg_dist[2 * qpx + 1] = valid ? d_coh : 0.0;
         }
     }
     }   // wave 0
@@ -1355,7 +1227,7 @@ __global__ __launch_bounds__(256) void k_exact3(Fin3 f, Scr3 sc, Nx3 nx) {
 // per pixel: the winner is the lexicographic minimum of k_match3's partials (order free); the
 // 15 coherence candidates' and the winner's rows are read once, lane-parallel over (row,
 // feature); their plain and weighted squared terms go to LDS, and 31 threads sum one row each
-// (Pw165): the same values as row3_dist.
+// (Pw165); then c3_decide and the B' store as k_exact3.
 __global__ __launch_bounds__(256) void k_finish3w(Fin3 f, const Best *__restrict__ part, int nb) {
     __shared__ double qs[D3P], wsh[D3P];
     __shared__ double tp[15][D3], tw[16][D3];   // coherence rows: plain, weighted (+ winner)
@@ -1366,50 +1238,16 @@ __global__ __launch_bounds__(256) void k_finish3w(Fin3 f, const Best *__restrict
     __shared__ long long ri[4];
     const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int y = f.y_lo + m, x = f.t - 3 * y;
-    const int W = f.W, Ah = f.Ah, Aw = f.Aw;
-    const long hw = (long)Ah * Aw;
-    const bool first = y == 0 && x == 0;
-    // the query, the weights, the partials' minimum and the
-    // candidates' rows: one round trip
+    // the query, the weights, the coherence candidates' rows (from s / im) and the partials'
+    // minimum: one round trip
     if (tid < D3P) {
         qs[tid] = f.q3[(long)m * D3P + tid];
         wsh[tid] = tid < D3 ? f.weights[tid] : 0.0;
     }
-    // the coherence candidates' rows (their s / im in the same round trip as the rest)
-    if (tid < 15) {
-        long long cix = -1;
-        int cr = 0, cc = 0, cim = 0;
-        if (!first) {
-            const int rr = y - 2 + tid / 5, rc = x - 2 + tid % 5;
-            if (rr >= 0 && rc >= 0 && rc < W && (rr < y || rc < x)) {
-                const long sidx = (long)rr * W + rc;
-                const int sr = f.s[2 * sidx] + y - rr, sc = f.s[2 * sidx + 1] + x - rc;
-                if (sr >= 0 && sr < Ah && sc >= 0 && sc < Aw) {
-                    const int simg = f.im[sidx];
-                    cix = ((long)Ah * simg + sr) * Aw + sc;
-                    cr = sr; cc = sc; cim = simg;
-                }
-            }
-        }
-        rix[tid] = cix;
-        rpos[tid][0] = cr; rpos[tid][1] = cc; rpos[tid][2] = cim;
-    }
-    double bd = INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
-    for (int i = tid; i < nb; i += 256) best3(bd, bi, part[(long)m * nb + i].d, part[(long)m * nb + i].idx);
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(bd, o);
-        const long long oi = __shfl_xor(bi, o);
-        best3(bd, bi, od, oi);
-    }
-    if (lane == 0) { rd[wv] = bd; ri[wv] = bi; }
+    if (tid < 15) c3_window(tid, y, x, f, rix, rpos);
+    const long long app = block_best(part + (long)m * nb, nb, rd, ri).idx;
+    if (tid == 0) rix[15] = app;
     __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w) best3(rd[0], ri[0], rd[w], ri[w]);
-        rix[15] = ri[0];
-    }
-    __syncthreads();
-    const long long app = rix[15];
     // the terms: (row j, feature k) pairs spread over the block, each row read once
     for (int e = tid; e < 16 * D3; e += 256) {
         const int j = e / D3, k = e - j * D3;
@@ -1434,43 +1272,8 @@ __global__ __launch_bounds__(256) void k_finish3w(Fin3 f, const Best *__restrict
     }
     __syncthreads();
     if (wv != 0) return;
-    // coherence: the first minimum of the plain distances in (row, col) candidate order
-    double cd = lane < 15 && rix[lane] >= 0 ? sump[lane] : INFINITY;
-    long long cl = lane < 15 && rix[lane] >= 0 ? lane : 0x7fffffffffffffffLL;
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(cd, o);
-        const long long ol = __shfl_xor(cl, o);
-        best3(cd, cl, od, ol);
-    }
-    const bool valid = cl != 0x7fffffffffffffffLL;
-    const int win = valid ? (int)cl : 0;
-    const int wr = rpos[win][0], wc = rpos[win][1], wim = rpos[win][2];
-    const double d_app = valid ? sumw[15] : 0.0, d_coh = valid ? sumw[win] : 0.0;
-    long img = app / hw;
-    long rem = app - img * hw;
-    const int ar = (int)(rem / Aw), ac = (int)(rem - (long)(rem / Aw) * Aw);
-    int pr = ar, pc = ac;
-    if (valid && d_coh <= d_app * f.kappa_factor) { pr = wr; pc = wc; img = wim; }
-    const long qpx = (long)y * W + x;
-    if (lane < 3)
-        f.Bp_lg[qpx * 3 + lane] = f.Ap_lg[((img * hw) + (long)pr * Aw + pc) * 3 + lane];
-    if (lane == 0) {
-        f.s[2 * qpx] = pr;
-        f.s[2 * qpx + 1] = pc;
-        f.im[qpx] = (int32_t)img;
-        if (f.dbg_px) {
-            int32_t *o = f.dbg_px + 7 * qpx;
-            o[0] = ar;
-            o[1] = ac;
-            o[2] = valid ? wr : 0;
-            o[3] = valid ? wc : 0;
-            o[4] = valid ? y - 2 + win / 5 : 0;
-            o[5] = valid ? x - 2 + win % 5 : 0;
-            o[6] = valid;
-            f.dbg_dist[2 * qpx] = valid ? d_app : 0.0;
-            f.dbg_dist[2 * qpx + 1] = valid ? d_coh : 0.0;
-        }
-    }
+    const long src = c3_decide(f, y, x, lane, app, sumw[15], sump, sumw, rix, rpos);
+    if (lane < 3) f.Bp_lg[((long)y * f.W + x) * 3 + lane] = f.Ap_lg[src + lane];
 }
 
 // per-pixel API helpers (algorithms.py:92-135) for 165-dim rows: the coherence argmin over n
@@ -1525,12 +1328,12 @@ static inline int match3_blocks(long nrows) { return (int)((nrows + M3_ROWS - 1)
 static std::atomic<int> g_color16{env_int("IA_COLOR16", 1)};
 static unsigned long long *g_c3_stats = nullptr;   // diagnostic counters (ia_diag_color16_stats)
 
-// the synthesis workspace: q3 | best | partials (fp64 search) | q16 | qn | tile minima, and for
+// the synthesis workspace: q3 | partials (fp64 search) | q16 | qn | tile minima, and for
 // the fused R16c tail (k_exact3<true>) the odd waves' query set, the control words and the
 // decision granules
 struct Ws3 {
     double *q3;
-    Best *best, *part;
+    Best *part;
     half8 *q16;              // the query tiles of either screen (C16_TILE >= R3_TILE)
     double *qn, *nsk;
     float *smin;
@@ -1541,18 +1344,14 @@ struct Ws3 {
 };
 constexpr int C3_CTL_ERR = 2;
 // the fused colour tail (k_exact3<true>: the next wave's query rows from the exact stage's
-// launch; IA_C3_FUSE, default 1) on R16c levels
-static inline bool c3_fuse() {
-    static const int v = env_int("IA_C3_FUSE", 1);
-    return v != 0;
-}
+// launch; IA_C3_FUSE, default 1) on R16c levels; read per level (Level3::init)
+static inline bool c3_fuse() { return env_int("IA_C3_FUSE", 1) != 0; }
 static_assert(C16_TILE >= R3_TILE, "query tiles");
 static inline size_t ws3_layout(int H, int W, long nrows, char *base, Ws3 *w) {
     const size_t M = (size_t)wave_max_queries(H, W), Mp = (M + 31) / 32 * 32;
     size_t o = 0;
     auto take = [&](size_t bytes) { char *p = base ? base + o : nullptr; o += align_up(bytes, 256); return p; };
     char *q3 = take(Mp * D3P * sizeof(double));
-    char *best = take(M * sizeof(Best));
     char *part = take(M * (size_t)match3_blocks(nrows) * sizeof(Best));
     char *q16 = take(Mp / 32 * C16_TILE * sizeof(half8));
     char *qn = take(Mp * sizeof(double));
@@ -1572,7 +1371,6 @@ static inline size_t ws3_layout(int H, int W, long nrows, char *base, Ws3 *w) {
         w->ctl = reinterpret_cast<unsigned *>(ctl);
         w->dbox = reinterpret_cast<unsigned long long *>(dbox);
         w->q3 = reinterpret_cast<double *>(q3);
-        w->best = reinterpret_cast<Best *>(best);
         w->part = reinterpret_cast<Best *>(part);
         w->q16 = reinterpret_cast<half8 *>(q16);
         w->qn = reinterpret_cast<double *>(qn);
@@ -1612,7 +1410,7 @@ struct Level3 {
         Bpsm = Img3{a->Bp_sm, a->B_hs, a->B_ws};
         Bplg = Img3{a->Bp_lg, H, W};
         v = db3_view(const_cast<void *>(a->db), a->nrows);
-        f = Fin3{v.rows, w.q3, w.best, a->src.Ap_lg, a->src.Ah, a->src.Aw,
+        f = Fin3{v.rows, w.q3, a->src.Ap_lg, a->src.Ah, a->src.Aw,
                  0, 0, W, a->weights, a->kappa_factor, a->Bp_lg, a->s, a->im, a->dbg_px, a->dbg_dist};
         split = g_color16.load(std::memory_order_relaxed) != 0;
         ntiles = (int)v.ntiles;

@@ -1,6 +1,13 @@
-// ia_finish.h — per-pixel tail of one synthesis step (image_analogies.py:169-217), shared
-// by k_finish (ia_synth.hip; after the cross-rank exchange) and the fused single-GPU
-// exact stage k_rescore<true> (ia_match.hip).
+// ia_finish.h — per-pixel tail of one synthesis step (image_analogies.py:169-217 with
+// best_coherence_match and compute_distance, algorithms.py:92-135).  The tail core below is
+// channel-agnostic and written once: the luminance tails (coh_pick / finish_apply here, used
+// by ia_synth.hip and ia_match.hip) and the 3-channel ones (k_exact3, k_finish3w,
+// ia_color3.hip) differ only in how they compute the distances and in how many channels of
+// B' they write.  The fused kernels' xw_finish (ia_xwave.hip) keeps its own copy of the kappa
+// test and the record: on kappa_pick / tail_record k_xwave and k_xstrip (250 VGPRs) kept
+// every resource figure but were scheduled differently throughout, and the c4 A/B cannot
+// resolve the 0.3 % in question (profiles/r08_colour_tail_ab.txt), so their code stays as
+// it was.
 #pragma once
 #include "ia_internal.h"
 
@@ -19,56 +26,140 @@ __device__ __forceinline__ void fin_best(double &bd, long long &bi, double d, lo
     if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
 }
 
+// ---- the tail core ---------------------------------------------------------------------
+// Window position k (0..14 = the reference's product(rows, cols) order over rows y-2..y,
+// cols x-2..x+2) of query pixel (y, x): the candidate s(r*) + (q - r*) of the B' pixel r*
+// (algorithms.py:101-118).  row: its DB row, -1 where r* is not scanline-earlier, lies
+// outside B', or the candidate falls outside A'.  found(row) runs where there is a candidate,
+// inside the bounds branches: coh_pick's 55-load gather placed after the call behind a
+// row >= 0 test compiles to another schedule (85 instead of 152 VGPRs, not measured).
+struct CohPos {
+    long long row;
+    int r, c, im;
+};
+template <class F>
+__device__ __forceinline__ CohPos coh_pos(int k, int y, int x, int W, int Ah, int Aw,
+                                          const int32_t *s, const int32_t *im, F &&found) {
+    CohPos p{-1, 0, 0, 0};
+    const int rr = y - 2 + k / 5, rc = x - 2 + k % 5;
+    if (rr >= 0 && rc >= 0 && rc < W && (rr < y || rc < x)) {
+        const long sidx = (long)rr * W + rc;
+        const int sr = s[2 * sidx] + y - rr, sc = s[2 * sidx + 1] + x - rc;
+        if (sr >= 0 && sr < Ah && sc >= 0 && sc < Aw) {
+            p.im = im[sidx];
+            p.row = ((long)Ah * p.im + sr) * Aw + sc;
+            p.r = sr;
+            p.c = sc;
+            found(p.row);
+        }
+    }
+    return p;
+}
+__device__ __forceinline__ CohPos coh_pos(int k, int y, int x, int W, int Ah, int Aw,
+                                          const int32_t *s, const int32_t *im) {
+    return coh_pos(k, y, x, W, Ah, Aw, s, im, [](long long) {});
+}
+
+// One whole wave: lane k's plain distance d (+inf: no candidate) -> the first minimum in
+// lane order (np.argmin, algorithms.py:126-128).  False: no lane has a candidate (win = 0).
+__device__ __forceinline__ bool coh_first_min(double d, int lane, int &win) {
+    long long bl = d < INFINITY ? lane : 0x7fffffffffffffffLL;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(d, o);
+        const long long ol = __shfl_xor(bl, o);
+        fin_best(d, bl, od, ol);
+    }
+    const bool valid = bl != 0x7fffffffffffffffLL;
+    win = valid ? (int)bl : 0;
+    return valid;
+}
+// the CohSel of coh_first_min's result for pixel (y, x): p the CohPos of window position win,
+// dcoh its weighted distance
+__device__ __forceinline__ CohSel coh_sel(const CohPos &p, int win, bool valid, int y, int x,
+                                          double dcoh) {
+    return CohSel{p.row, p.r, p.c, p.im, y - 2 + win / 5, x - 2 + win % 5, valid, dcoh};
+}
+
+// The kappa test (image_analogies.py:200-211): the pixel's source is the coherence candidate
+// c when its weighted distance is within kappa_factor of the exact winner's (d_app), else the
+// exact winner, DB row app of a database of hw = Ah x Aw pixels per image.
+struct TailSel {
+    int img, pr, pc;     // the chosen source: A' image and pixel
+    int ar, ac;          // the exact winner's own pixel (debug record)
+};
+__device__ __forceinline__ TailSel kappa_pick(long long app, long hw, int Aw, double d_app,
+                                              const CohSel &c, double kappa_factor) {
+    const long img = app / hw;
+    const long rem = app - img * hw;
+    const int ar = (int)(rem / Aw), ac = (int)(rem - (long)(rem / Aw) * Aw);
+    if (c.valid && c.dcoh <= d_app * kappa_factor) return TailSel{c.wim, c.wr, c.wc, ar, ac};
+    return TailSel{(int)img, ar, ac, ar, ac};
+}
+
+// One lane: s and im of pixel q = y W + x (image_analogies.py:215-217; the B' value is the
+// caller's: one channel or three) and, with the debug outputs (:141-159, 222-240), per pixel
+// {p_app row, col, p_coh row, col, r* row, col, has coherence} and {d_app, d_coh} (zeros
+// where there is no coherence candidate, as the reference).
+__device__ __forceinline__ void tail_record(long q, const TailSel &p, const CohSel &c, double d_app,
+                                            int32_t *s, int32_t *im, int32_t *dbg_px,
+                                            double *dbg_dist) {
+    if (dbg_px) {
+        int32_t *o = dbg_px + 7 * q;
+        o[0] = p.ar;
+        o[1] = p.ac;
+        o[2] = c.valid ? c.wr : 0;
+        o[3] = c.valid ? c.wc : 0;
+        o[4] = c.valid ? c.rr : 0;
+        o[5] = c.valid ? c.rc : 0;
+        o[6] = c.valid;
+        dbg_dist[2 * q] = c.valid ? d_app : 0.0;
+        dbg_dist[2 * q + 1] = c.valid ? c.dcoh : 0.0;
+    }
+    s[2 * q] = p.pr;
+    s[2 * q + 1] = p.pc;
+    im[q] = p.img;
+}
+
+// One 256-thread block: the lexicographic (distance, row) minimum over p[0 .. nb), valid in
+// every thread (sd / si: 4 LDS words each; one barrier inside).
+__device__ __forceinline__ Best block_best(const Best *p, int nb, double *sd, long long *si) {
+    double bd = INFINITY;
+    long long bi = 0x7fffffffffffffffLL;
+    for (int i = threadIdx.x; i < nb; i += 256) fin_best(bd, bi, p[i].d, p[i].idx);
+    for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(bd, o);
+        const long long oi = __shfl_xor(bi, o);
+        fin_best(bd, bi, od, oi);
+    }
+    if ((threadIdx.x & 63) == 0) { sd[threadIdx.x >> 6] = bd; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    bd = sd[0];
+    bi = si[0];
+    for (int w = 1; w < 4; ++w) fin_best(bd, bi, sd[w], si[w]);
+    return Best{bd, bi};
+}
+
+// ---- the luminance tail ------------------------------------------------------------------
 // Coherence half of the tail, executed by ONE 64-lane wave for query pixel m of wave t
 // (query in qs, LDS): best_coherence_match (algorithms.py:92-130) over the causal 3x5
-// window (lanes 0..14 = the reference's product(rows, cols) order) and the weighted
-// distance of its winner (algorithms.py:133-135).  Needs only s / im of earlier waves.
-// Result valid in every lane.
+// window (lanes 0..14) and the weighted distance of its winner (algorithms.py:133-135).
+// Needs only s / im of earlier waves.  Result valid in every lane.
 __device__ __forceinline__ CohSel coh_pick(const DbSrc &src, int m, const FinishArgs &f,
                                            const double *qs, int lane) {
     CohSel r{0, 0, 0, 0, 0, 0, 0, 0.0};
     const int y = f.y_lo + m, x = f.t - 3 * y;
     if (y == 0 && x == 0) return r;
-    const int W = f.W;
-    const int Ah = src.A.h, Aw = src.A.w;
+    CohPos p{-1, 0, 0, 0};
     double cd = INFINITY;
-    long long cl = 0x7fffffffffffffffLL;
-    long cix = -1;
-    int cr = 0, cc = 0, cim = 0;
-    if (lane < 15) {
-        const int rr = y - 2 + lane / 5, rc = x - 2 + lane % 5;
-        if (rr >= 0 && rc >= 0 && rc < W && (rr < y || rc < x)) {
-            const long sidx = (long)rr * W + rc;
-            const int sr = f.s[2 * sidx] + y - rr, sc = f.s[2 * sidx + 1] + x - rc;
-            if (sr >= 0 && sr < Ah && sc >= 0 && sc < Aw) {
-                const int simg = f.im[sidx];
-                cix = ((long)Ah * simg + sr) * Aw + sc;
-                cr = sr; cc = sc; cim = simg;
-                cd = sqrt(row_dist2(src, cix, qs));
-                cl = lane;
-            }
-        }
-    }
-    double bd = cd;
-    long long bl = cl;
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(bd, o);
-        const long long ol = __shfl_xor(bl, o);
-        fin_best(bd, bl, od, ol);
-    }
-    if (bl == 0x7fffffffffffffffLL) return r;
-    const int win = (int)bl;
-    r.wix = __shfl(cix, win);
-    r.wr = __shfl(cr, win);
-    r.wc = __shfl(cc, win);
-    r.wim = __shfl(cim, win);
-    r.rr = y - 2 + win / 5;
-    r.rc = x - 2 + win % 5;
-    r.valid = 1;
+    if (lane < 15)
+        p = coh_pos(lane, y, x, f.W, src.A.h, src.A.w, f.s, f.im,
+                    [&](long long row) { cd = sqrt(row_dist2(src, row, qs)); });
+    int win;
+    if (!coh_first_min(cd, lane, win)) return r;
+    p = CohPos{__shfl(p.row, win), __shfl(p.r, win), __shfl(p.c, win), __shfl(p.im, win)};
     double d = 0.0;
-    if (lane == 1) d = row_wdist(src, r.wix, qs, f.weights);
-    r.dcoh = __shfl(d, 1);
-    return r;
+    if (lane == 1) d = row_wdist(src, p.row, qs, f.weights);
+    return coh_sel(p, win, true, y, x, __shfl(d, 1));
 }
 
 // Weighted distance of the exact-match winner app (algorithms.py:133-135) for the kappa
@@ -84,43 +175,20 @@ __device__ __forceinline__ double app_wdist(const DbSrc &src, long long app, con
     return __shfl(d, 0);
 }
 
-// The rest of the tail: the kappa test (image_analogies.py:200-211) of the coherence
-// candidate c against the exact-match winner app (weighted distance d_app, app_wdist), and
-// the B' / s / im update (:213-217).  With the debug outputs (image_analogies.py:141-159,
-// 222-240): per pixel {p_app row, col, p_coh row, col, r* row, col, has coherence} and
-// {d_app, d_coh} (zeros where there is no coherence candidate, as the reference).
+// The rest of the tail: the kappa test of the coherence candidate c against the exact-match
+// winner app (weighted distance d_app, app_wdist), and the B' / s / im update with the debug
+// record (kappa_pick, tail_record).
 __device__ __forceinline__ void finish_apply(const DbSrc &src, long long app, int m,
                                              const FinishArgs &f, const CohSel &c, double d_app,
                                              int lane) {
     const int y = f.y_lo + m, x = f.t - 3 * y;
-    const int W = f.W;
     const int Aw = src.A.w;
     const long hw = src.hw;
-    app = app_clamp(app, f);
-    long img = app / hw;
-    long rem = app - img * hw;
-    int pr = (int)(rem / Aw), pc = (int)(rem - (long)(rem / Aw) * Aw);
-    if (c.valid && c.dcoh <= d_app * f.kappa_factor) {
-        pr = c.wr; pc = c.wc; img = c.wim;
-    }
+    const TailSel p = kappa_pick(app_clamp(app, f), hw, Aw, d_app, c, f.kappa_factor);
     if (lane == 0) {
-        const long q = (long)y * W + x;
-        if (f.dbg_px) {
-            int32_t *o = f.dbg_px + 7 * q;
-            o[0] = (int32_t)(rem / Aw);
-            o[1] = (int32_t)(rem - (long)(rem / Aw) * Aw);
-            o[2] = c.valid ? c.wr : 0;
-            o[3] = c.valid ? c.wc : 0;
-            o[4] = c.valid ? c.rr : 0;
-            o[5] = c.valid ? c.rc : 0;
-            o[6] = c.valid;
-            f.dbg_dist[2 * q] = c.valid ? d_app : 0.0;
-            f.dbg_dist[2 * q + 1] = c.valid ? c.dcoh : 0.0;
-        }
-        f.Bp_lg[q] = src.Ap.lg[img * hw + (long)pr * Aw + pc];
-        f.s[2 * q] = pr;
-        f.s[2 * q + 1] = pc;
-        f.im[q] = (int32_t)img;
+        const long q = (long)y * f.W + x;
+        f.Bp_lg[q] = src.Ap.lg[p.img * hw + (long)p.pr * Aw + p.pc];
+        tail_record(q, p, c, d_app, f.s, f.im, f.dbg_px, f.dbg_dist);
     }
 }
 

@@ -3,6 +3,8 @@ num_ch = 3, 165-dim rows of channel-interleaved windows, algorithms.py:11-47) on
 against the numpy oracle: the feature arrays, the per-pixel API (exact 1-NN, coherence,
 weighted distance), whole-level synthesis (B' in all three channels, s, im and the debug
 lists) and image_analogies_main end to end from colour image files."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -202,16 +204,10 @@ def _screen3r_vs_fp64(scale):
     return worst, idx
 
 
-@pytest.mark.parametrize('pipeline', [True, False])
-@pytest.mark.parametrize('matcher', [1, 0])
-@pytest.mark.parametrize('n_ap,k', [(1, 1.0), (2, 25.0)])
-def test_synthesis3_vs_oracle(gpu, color16, n_ap, k, matcher, pipeline):
-    """Whole-level 3-channel synthesis: B' (all channels), s, im and the debug lists equal
-    the oracle's scanline run (image_analogies.py:130-240 with num_ch = 3), with the
-    split-f16 screen + exact stage (1) and the exhaustive fp64 search (0), the levels
-    pipelined (ia_synth_levels3) or one at a time (ia_synth_level3)."""
-    import image_analogies as ia
-    color16(matcher)
+@functools.lru_cache(maxsize=None)
+def synthesis3_reference(n_ap, k):
+    """test_synthesis3_vs_oracle's inputs and the oracle's run of them: computed once per
+    (n_ap, k), shared by every dispatch case, never modified."""
     A_pyr, Ap_list, B_pyr, Bp_pyr, L = inputs(83 + n_ap, (36, 44), (30, 34), n_ap=n_ap)
     w = o.compute_weights(3, 5, 12, 3)
     As = o.create_index(A_pyr, Ap_list, L)
@@ -222,6 +218,26 @@ def test_synthesis3_vs_oracle(gpu, color16, n_ap, k, matcher, pipeline):
         s, im = o.synthesize_level(level, L, A_pyr, Ap_list, B_pyr, Bp_ref, As[level], w, k,
                                    debug=dbg)
         ref[level] = (s, im, dbg)
+    return A_pyr, Ap_list, B_pyr, Bp_pyr, L, w, Bp_ref, ref
+
+
+@pytest.mark.parametrize('pipeline', [True, False])
+@pytest.mark.parametrize('matcher,rot,fuse', [(1, '1', '1'), (0, '1', '1'), (1, '1', '0'), (1, '0', '1')],
+                         ids=['1', '0', '1-unfused', '1-split'])
+@pytest.mark.parametrize('n_ap,k', [(1, 1.0), (2, 25.0)])
+def test_synthesis3_vs_oracle(gpu, color16, monkeypatch, n_ap, k, matcher, rot, fuse, pipeline):
+    """Whole-level 3-channel synthesis: B' (all channels), s, im and the debug lists equal
+    the oracle's scanline run (image_analogies.py:130-240 with num_ch = 3) on all four
+    dispatch branches of a level's wave: the rotated screen with the fused tail
+    (k_exact3<true>; matcher 1, the default), the same with IA_C3_FUSE=0 (k_query3r +
+    k_exact3<false>), the split-f16 screen (IA_DB_ROT=0; there IA_C3_FUSE changes nothing, so
+    that pair is not run) and the exhaustive fp64 search (matcher 0: k_match3 + k_finish3w);
+    the levels pipelined (ia_synth_levels3) or one at a time (ia_synth_level3)."""
+    import image_analogies as ia
+    color16(matcher)
+    monkeypatch.setenv('IA_DB_ROT', rot)
+    monkeypatch.setenv('IA_C3_FUSE', fuse)
+    A_pyr, Ap_list, B_pyr, Bp_pyr, L, w, Bp_ref, ref = synthesis3_reference(n_ap, k)
     Bp_dev = [dev(b) for b in Bp_pyr]
     out = ia.synthesize_dev([dev(p) for p in A_pyr], [[dev(p) for p in q] for q in Ap_list],
                             [dev(p) for p in B_pyr], Bp_dev, L, k, w, debug=True, pipeline=pipeline)
