@@ -55,7 +55,7 @@ class IaSynthArgs(ctypes.Structure):
                 ('kappa_factor', ctypes.c_double), ('s', _dp), ('im', _dp),
                 ('workspace', _dp), ('comm', _dp), ('lsh', ctypes.POINTER(IaLsh)),
                 ('flags', ctypes.c_int), ('tag', ctypes.c_int), ('dbg_px', _dp),
-                ('dbg_dist', _dp), ('dbi', _dp), ('dbr', _dp), ('rot', _dp)]
+                ('dbg_dist', _dp), ('dbi', _dp), ('dbr', _dp), ('rot', _dp), ('dbk', _dp)]
 
 
 class IaShardDb(ctypes.Structure):
@@ -101,6 +101,10 @@ _SIGS = {
     'ia_db_cov': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long, _dp, _dp, _dp]),
     'ia_db_build_rot': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long, _dp, _dp,
                                        _dp, _dp, _dp]),
+    'ia_db_rotk_bytes': (ctypes.c_size_t, [ctypes.c_long]),
+    'ia_db_rotk_applies': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long]),
+    'ia_db_build_rotk': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long, _dp, _dp,
+                                        _dp, _dp, _dp]),
     'ia_db_build': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long,
                                    _dp, _dp, _dp, _dp]),
     'ia_db_image_bytes': (ctypes.c_size_t, [ctypes.POINTER(IaSrcLevel), ctypes.c_long,
@@ -191,6 +195,11 @@ _SIGS = {
     'ia_diag_peer_trace': (ctypes.c_int, [_dp, _dp]),
     'ia_diag_screen16r': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long, _dp, _dp,
                                          _dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
+    'ia_diag_screen16k': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long, _dp, _dp,
+                                         _dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
+    'ia_diag_set_compact_min_rows': (ctypes.c_long, [ctypes.c_long]),
+    'ia_diag_wave_compact': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    'ia_diag_compact_waves': (ctypes.c_long, []),
     'ia_diag_wave_rows': (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]),
     'ia_diag_pipe_schedule': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3 + [ctypes.c_int] * 3 +
                               [ctypes.POINTER(ctypes.c_int), ctypes.c_int]),

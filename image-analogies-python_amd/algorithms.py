@@ -124,7 +124,7 @@ class LevelIndex:
                                             _ia.ptr(self.amax), _ia.ptr(self.dbi), st),
                       'ia_db_build_image')
         self.lsh = None
-        self.dbr = self.rot = None
+        self.dbr = self.rot = self.dbk = None
         if rot and lib.ia_db_rot_applies(ctypes.byref(self.src), self.row0, self.nrows):
             self.build_rot()
 
@@ -148,6 +148,12 @@ class LevelIndex:
         _ia.check(lib.ia_db_build_rot(ctypes.byref(self.src), self.row0, self.nrows,
                                       _ia.ptr(self.center), _ia.ptr(self.rot), _ia.ptr(self.amax),
                                       _ia.ptr(self.dbr), st), 'ia_db_build_rot')
+        # the compact rotated DB (24 leading components, 64 B per row) where the level takes it
+        if lib.ia_db_rotk_applies(ctypes.byref(self.src), self.row0, self.nrows):
+            self.dbk = torch.empty(lib.ia_db_rotk_bytes(self.nrows), dtype=torch.uint8, device=dev)
+            _ia.check(lib.ia_db_build_rotk(ctypes.byref(self.src), self.row0, self.nrows,
+                                           _ia.ptr(self.center), _ia.ptr(self.rot), _ia.ptr(self.amax),
+                                           _ia.ptr(self.dbk), st), 'ia_db_build_rotk')
         return self
 
     def dbi_ptr(self):

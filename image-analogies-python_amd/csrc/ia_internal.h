@@ -294,6 +294,13 @@ struct XArgs {
     gptr<const float> rot;        // R16 level (k_xstrip only, nullable): the rotation; q16n rows in
                                   // the R16 layout, q64 slot 55 = |kappa_skip|^2, amax[1] = A_skip
     gptr<const unsigned char> askc;  // R16 level: per-segment skip codes (r16_askc, ia_rot16.h)
+    // a level with compact waves (ia_rot16.h RK_*): rk != 0, the next query rows carry the compact
+    // operands too; a compact wave (k_xstrip<false, true, true>; nullable otherwise): the
+    // segments' rest-norm codes and Rmax, and this wave's q16 rows (|kappa_rest|^2)
+    int rk;
+    gptr<const unsigned char> restc;
+    gptr<const float> rmax;
+    gptr<const _Float16> q16;
 };
 // k_xwave phase stamps (IA_XW_TRACE=<level tag>, ia_diag_xwave_trace): s_memrealtime (100
 // MHz) at XW_TRACE_N - 1 points of the pixels with ticket < XW_TRACE_PX of waves < XW_TRACE_T;
@@ -332,9 +339,13 @@ int launch_query_wave(const ImgPair &B, const ImgPair &Bp, int t, int y_lo, int 
                       const float *amax, _Float16 *q16, hipStream_t st, const float *rot = nullptr);
 // the rotated split-f16 screen (R16, ia_screen16r.hip, ia_rot16.h) of M queries (q16 in the
 // R16 layout) over a rotated DB (ia_db_build_rot) -> segmin[M][db_nsegs(nrows)], the same
-// units as launch_screen16; jobs: a batch (each job's dbr, q16[parity], segmin)
+// units as launch_screen16; jobs: a batch (each job's dbr, q16[parity], segmin); compact: dbr is
+// the compact DB (ia_db_build_rotk) and the minima are lower bounds only (ia_rot16.h RK_*)
 int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Float16 *q16, int M,
-                     float *segmin, hipStream_t st, const XJob *jobs = nullptr, int njobs = 1, int parity = 0);
+                     float *segmin, hipStream_t st, const XJob *jobs = nullptr, int njobs = 1, int parity = 0,
+                     bool compact = false);
+// the compact form's row threshold (ia_diag_set_compact_min_rows; LONG_MAX: off)
+long compact_min_rows();
 // amax = max(amax, the split scale's bound of a level's four value ranges) (ia_features.hip);
 // part: DBB_BLOCKS x 8 doubles of scratch
 int launch_db_amax(const IaSrcLevel *src, const DbSrc &d, const double *center, float *amax,

@@ -23,6 +23,11 @@ static inline void wave_rows(int H, int W, int t, int &y_lo, int &M) {
     M = y_hi - y_lo + 1;
 }
 
+// Wave t may take the compact screen (ia_rot16.h RK_*) iff none of its pixels has B'
+// initialisation noise in its window's causal part, i.e. lies in row 0 (y = 0, x = t: t <= W - 1)
+// or column 0 (x = 0: t = 3y): those queries' noise is in the dropped components
+static inline bool wave_compact(int W, int t) { return t >= W && t % 3 != 0; }
+
 // the most queries of one wave, + 1 (the workspaces are sized by it)
 static inline int wave_max_queries(int H, int W) {
     const int byw = (W + 2) / 3;   // ceil(W/3)

@@ -154,12 +154,78 @@ __device__ __forceinline__ void r16_thresholds_rows(float emin, float amax0, flo
     if (split16_db_clamped(amax0)) { force_full = true; Trow = INFINITY; }
 }
 
+// ---- the compact screen (DESIGN.md §4d "compact"): the leading RK_C components only -------
+// 2P + 1 + C + 1 = 32 slots (P = 3, C = 24): ONE v_mfma_f32_16x16x32_f16 per 16x16 block and 64 B
+// per row.  Slot order as above: cross terms 0 .. 2P-1, RK_NL the norm's lo part, RK_M0 + k
+// main term k (k < C), RK_NH the norm's hi part; the norm is |rho_C|^2 (the kept components'),
+// so the screen value is e_C(r) = |rho_C|^2 - 2 rho_C.kappa_C in the units of the full screen.
+// With k = |kappa_rest| (components C..54 of the query) and R_j >= |rho_rest| over segment j,
+//   D(r) = |rho - kappa|^2 (1 +- 15u) = e_C(r) + |kappa_C|^2 + |rho_rest - kappa_rest|^2 +- ...
+//        >= e_C(r) + |q'|^2 - k^2 + max(0, k - R_j)^2 - 15u ((A + |q'|)^2 + |q'|^2)
+// (V_f V_f^T = I up to 15u in norm: |rho - kappa|^2 against D, and |kappa|^2 against |q'|^2), so a
+// segment's compact minimum m_j gives only a LOWER bound L_j of its rows' distances:
+//   L_j = m_j - eps_j + |q'|^2 - k^2 + max(0, k - R_j)^2,
+//   eps_j = u (360 A|q'| + RK_EPS_A2 A^2 + 32 |q'|^2) + 2^-9 1.01 A_skip,j |kappa_skip|.
+// The rounding terms are r16_eps's restricted to the kept components (representation, f16 flush
+// and accumulation bound those of the 64-slot form term by term: fewer slots, one MFMA of K = 32
+// instead of two; A and |q'| bound |rho_C| and |kappa_C|; A_skip,j and |kappa_skip| of components
+// P..54 bound those of P..C-1, so the 64-slot form's codes serve); the rotation's 30u A|q'| now
+// pays for D against |rho - kappa|^2, whose other parts are 15u A^2 (85.4 + 15 <= RK_EPS_A2) and
+// 30u |q'|^2.  The exact stage (k_xstrip<.., true, true>) rescores one segment exactly first
+// (any: it takes the least L_j), U = its fp64 minimum, and then every segment with L_j <= U:
+// the oracle's winner r_o (segment o) has L_o <= D(r_o) <= U.
+// Layouts.  DB: per 32-row tile 4 groups x 32 rows x half8 (group g = slots 8g .. 8g + 7: lane
+// quarter g's operand), RK_ROW_B per row; then per segment R_j (fp32, rounded up), then a code
+// r_j with Rmax r_j / 255 >= R_j (u8), then Rmax (fp32).  Query: the same q16 row as the 64-slot
+// operands, which fill its first 8 half8: compact slot s is f16 RK_Q_F16 + s, and k^2 (fp64)
+// sits at byte RK_Q_REST_B.
+constexpr int RK_C = 24;                       // kept components
+constexpr int RK_NL = 2 * R16_P, RK_M0 = RK_NL + 1, RK_NH = RK_M0 + RK_C;
+constexpr int RK_SLOTS = 32;
+constexpr int RK_TILE_H8 = RK_SLOTS / 8 * 32;  // half8 per 32-row tile (2 KiB)
+constexpr int RK_ROW_B = RK_SLOTS * 2;
+constexpr int RK_Q_F16 = 64, RK_Q_REST_B = 192;
+constexpr bool RK_BUILT = R16_S16 && RK_NH == RK_SLOTS - 1;   // P = 3, the 16x16x32 shape
+static_assert(R16_SLOTS <= RK_Q_F16 || !RK_BUILT, "the compact operands follow the 64-slot ones");
+constexpr double RK_EPS_A2 = 110.0;
+static inline size_t rk_rseg_off(long nrows) { return (size_t)db_rows_padded(nrows) * RK_ROW_B; }
+static inline size_t rk_code_off(long nrows) { return rk_rseg_off(nrows) + img_align((size_t)db_nsegs(nrows) * 4); }
+static inline size_t rk_rmax_off(long nrows) { return rk_code_off(nrows) + img_align((size_t)db_nsegs(nrows)); }
+static inline size_t rk_bytes(long nrows) { return rk_rmax_off(nrows) + 256; }
+__device__ __forceinline__ double rk_eps0(double A, double nqq) {
+    constexpr double U32 = 5.9604644775390625e-08;
+    return U32 * (360.0 * A * sqrt(nqq) + RK_EPS_A2 * A * A + 32.0 * nqq);
+}
+// The selection in screen units (2^e2), given U = the seed segment's exact minimum distance:
+// segment j (minimum m, skip code c, rest code r) is a candidate iff
+//   m <= T0 + K c - S max(0, k - Rs r)^2,  T0 = 2^e2 (U - |q'|^2 + k^2 + eps_0 + slack),
+// K = r16_kseg, S = 2^e2, Rs = Rmax / 255; force_full as r16_tseg0.
+struct RkSel {
+    double T0, K, S, k, Rs;
+};
+__device__ __forceinline__ RkSel rk_select(double U, float amax0, float askip, float rmax, double nqq, double nsk,
+                                           double nrest, bool &force_full) {
+    const double A = (double)amax0;
+    const Split16Db sc = split16_db_scale(amax0);
+    const int eq = split16_q_scale(nqq, sc.R);
+    const int e2 = sc.ea + eq;
+    const double slack = 1e-11 * (U + nqq + A * A);
+    force_full = eq + sc.R < -10 || split16_db_clamped(amax0);
+    return RkSel{ldexp(U - nqq + nrest + rk_eps0(A, nqq) + slack, e2), r16_kseg(amax0, askip, nqq, nsk),
+                 ldexp(1.0, e2), sqrt(nrest), (double)rmax / 255.0};
+}
+__device__ __forceinline__ bool rk_take(const RkSel &s, float m, unsigned c, unsigned r) {
+    const double g = fmax(s.k - s.Rs * (double)r, 0.0);
+    return (double)m <= fma(s.K, (double)c, s.T0) - s.S * g * g;
+}
+
 // lane-parallel query row (64 lanes): d = this lane's centred feature q'_k (lane k < 55),
 // nq = |q'|^2 (every lane).  kappa_j = sum_k V[k][j] d_k in fp64 (lane j), split into the
-// row's slots; returns |kappa_skip|^2 = sum_{j >= R16_P} kappa_j^2 (every lane).  rot: the
+// row's slots (the 64-slot operands and, with compact, the compact ones and |kappa_rest|^2);
+// returns |kappa_skip|^2 = sum_{j >= R16_P} kappa_j^2 (every lane).  rot: the
 // fp32 rotation (global or LDS); dq: 64 doubles of wave-private LDS.
 __device__ __forceinline__ double r16_write_query(_Float16 *row, int lane, double d, double nq, float amax,
-                                                  const float *rot, double *dq) {
+                                                  const float *rot, double *dq, bool compact = false) {
     dq[lane] = lane < IA_D ? d : 0.0;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
@@ -189,12 +255,28 @@ __device__ __forceinline__ double r16_write_query(_Float16 *row, int lane, doubl
             row[r16_qpos(2 * lane)] = h;
             row[r16_qpos(2 * lane + 1)] = l;
         }
+        if (RK_BUILT && compact) {
+            if (lane < RK_C) row[RK_Q_F16 + RK_M0 + lane] = h;
+            if (lane < R16_P) {
+                row[RK_Q_F16 + 2 * lane] = h;
+                row[RK_Q_F16 + 2 * lane + 1] = l;
+            }
+        }
     } else if (lane == IA_D) {
         const _Float16 n = (_Float16)ldexpf(1.f, eq + sc.R);
         row[r16_qpos(R16_NL)] = n;
         row[r16_qpos(R16_NH)] = n;
+        if (RK_BUILT && compact) {
+            row[RK_Q_F16 + RK_NL] = n;
+            row[RK_Q_F16 + RK_NH] = n;
+        }
     } else if (lane > IA_D && R16_NH + (lane - IA_D) < R16_SLOTS) {
         row[r16_qpos(R16_NH + (lane - IA_D))] = (_Float16)0.f;   // the zero slots
+    }
+    if (RK_BUILT && compact) {
+        double r2 = (lane >= RK_C && lane < IA_D) ? kap * kap : 0.0;
+        for (int o = 32; o > 0; o >>= 1) r2 += __shfl_xor(r2, o);
+        if (lane == 0) *reinterpret_cast<double *>(reinterpret_cast<char *>(row) + RK_Q_REST_B) = r2;
     }
     return s2;
 }

@@ -5,7 +5,9 @@
 // k_screen16r: at P = 3 (the default, IA_R16_SHAPE = 16) two v_mfma_f32_16x16x32_f16 per
 // 16 x 16 (rows x queries) block, else R16_MFMA v_mfma_f32_32x32x16_f16 per 32x32 tile (the
 // split-f16 screen of ia_screen16.hip needs 11), same segment minima units, so the exact stage
-// (k_xstrip) is unchanged apart from its bound (ia_rot16.h r16_eps, per shape).
+// (k_xstrip) is unchanged apart from its bound (ia_rot16.h r16_eps, per shape).  The compact
+// form (k_screen16c over ia_db_build_rotk's DB, ia_rot16.h RK_*): the 24 leading components in 32
+// slots, one MFMA per block, 64 B per row, for the waves whose exact stage takes lower bounds.
 //
 // The screen's structure is the row form's of ia_screen16.hip (k_screen16): queries are the
 // stationary MFMA B operand (half8 per query block and lane); the DB streams through LDS in
@@ -281,6 +283,44 @@ __device__ __forceinline__ void r16_stage_s16(const half8 *sb, const half8 (&bq)
     });
 }
 
+// ---- the compact form's stage (ia_rot16.h RK_*): 32 slots, ONE MFMA per (16 rows, 16 queries)
+// chain; the same chains, order, lag and minima layout as r16_stage_s16.  Lane l's operand of row
+// block v: row 16 (v % 2) + l % 16 of tile v / 2, slots 8 (l / 16) .. + 7 = group l / 16
+__device__ __forceinline__ int s16k_aoff(int v, int lane) {
+    return (v >> 1) * RK_TILE_H8 + (lane >> 4) * 32 + 16 * (v & 1) + (lane & 15);
+}
+template <int G, int W, int NS>
+__device__ __forceinline__ void r16_stage_s16k(const half8 *sb, const half8 (&bq)[NS][1], float (&mn)[NS], int lane) {
+    constexpr int NC = c16_count<G, W>();
+    const floatx4 zero = {};
+    half8 a[2];
+    floatx4 acc[S16_NACC];
+    a[0] = sb[s16k_aoff(c16_v<G, W>(0), lane)];
+    sfor<0, NC>([&](auto cc) {
+        constexpr int c = decltype(cc)::value;
+        constexpr int k = c16_k<G, W>(c), ab = c16_vo<G, W>(c) & 1, cb = c % S16_NACC;
+        constexpr int cf = c - S16_LAG, fb = (c + 1) % S16_NACC;
+        constexpr bool rd = c16_first<G, W>(c) && c16_next<G, W>(c) >= 0;
+        if constexpr (rd) a[ab ^ 1] = sb[s16k_aoff(c16_v<G, W>(c16_next<G, W>(c)), lane)];
+        acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[ab], bq[k][0], zero, 0, 0, 0);
+        if constexpr (cf >= 0) {
+            constexpr int kf = c16_k<G, W>(cf);
+            mn[kf] = fminf(fminf(mn[kf], fminf(acc[fb][0], acc[fb][1])), fminf(acc[fb][2], acc[fb][3]));
+        }
+        if constexpr (IA_R16_PIN) {
+            if constexpr (rd) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                     // MFMA
+            if constexpr (cf >= 0) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    });
+    sfor<(NC > S16_LAG ? NC - S16_LAG : 0), NC>([&](auto cc) {
+        constexpr int c = decltype(cc)::value;
+        const floatx4 &x = acc[c % S16_NACC];
+        mn[c16_k<G, W>(c)] = fminf(fminf(mn[c16_k<G, W>(c)], fminf(x[0], x[1])), fminf(x[2], x[3]));
+    });
+}
+
 // LDS integer min as inline asm: the compiler's waitcnt pass treats an LDS atomic as a store
 // that may alias the DB stages' LDS-DMA destination and drains every stage in flight before
 // it (s_waitcnt vmcnt(0) at each segment close); smin and the stage ring never overlap
@@ -336,17 +376,26 @@ __device__ __forceinline__ void stage_barrier() {
 // minima are staged for SPC_STAGE segments at a time (flushed to segmin as soon as they
 // close) to leave the LDS for the ring.
 
-template <int G, int W>
+// CMP: the compact form (RK_TILE_H8 per tile, one MFMA per chain; stages of 8 KiB)
+template <int G, int W, bool CMP = false>
 __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *sbuf, int *smin,
                                          const StageMap &sm, long chunk, int s0, int nstage, int tps,
                                          const half8 *__restrict__ q16, float *__restrict__ segmin,
                                          long seg0, long nseg, int q0, int M) {
+    static_assert(!CMP || RK_BUILT, "the compact form needs the 16x16x32 shape at P = 3");
     constexpr int NS = R16_S16 ? c16_ns<G, W>() : bal_ns(G, W);
     constexpr int T0 = bal_t0(G, W);
+    // half8 per tile and stage, 1 KiB pieces each wave copies per stage
+    constexpr int TH8 = CMP ? RK_TILE_H8 : R16_TILE_H8, SH8 = STAGE_TILES * TH8, NP = SH8 / 256;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    half8 bq[NS][R16_S16 ? 2 : R16_MFMA];
-    if constexpr (R16_S16) {
+    half8 bq[NS][CMP ? 1 : R16_S16 ? 2 : R16_MFMA];
+    if constexpr (CMP) {
+        // query block T + k, lane l: query 16 (T + k) + l % 16, compact slots 8 (l / 16) .. + 7
+#pragma unroll
+        for (int k = 0; k < NS; ++k)
+            bq[k][0] = q16[(long)((c16_t0<G, W>() + k) * 16 + (lane & 15)) * Q16_ROW + RK_Q_F16 / 8 + (lane >> 4)];
+    } else if constexpr (R16_S16) {
         // query block T + k, lane l: query 16 (T + k) + l % 16, slots 32 n + 8 (l / 16) .. + 7,
         // i.e. the half8 (l / 16) % 2 * R16_MFMA + 2n + (l / 16) / 2 of its q16 row
         const int q = lane >> 4, c = lane & 15;
@@ -367,10 +416,10 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
     }
     // one stage = 4 consecutive tiles: 4 R16_MFMA wave-instructions of 1 KiB, R16_MFMA per wave
     auto issue = [&](int s) {
-        const half8 *src = db16 + (stage_lrow(sm, chunk, s0 + s) >> 5) * R16_TILE_H8 + W * 64 + lane;
-        half8 *dst = sbuf + (s % R16_RING) * STAGE_H8 + W * 64;
+        const half8 *src = db16 + (stage_lrow(sm, chunk, s0 + s) >> 5) * TH8 + W * 64 + lane;
+        half8 *dst = sbuf + (s % R16_RING) * SH8 + W * 64;
 #pragma unroll
-        for (int k = 0; k < R16_MFMA; ++k)
+        for (int k = 0; k < NP; ++k)
             __builtin_amdgcn_global_load_lds((const void *)(src + k * 256), (void *)(dst + k * 256), 16, 0, 2);
     };
     float mn[NS];
@@ -381,17 +430,20 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
     for (int s = 0; s < R16_RING - 1; ++s)
         if (s < nstage) issue(s);
     // stage 0 landed (the later stages' loads may stay in flight)
-    if (nstage > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(R16_MFMA * (R16_RING - 2)) : "memory");
+    if (nstage > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (R16_RING - 2)) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     stage_barrier();
     for (int s = 0; s < nstage; ++s) {
         const bool more = s + R16_RING - 1 < nstage;
         if (more) issue(s + R16_RING - 1);   // into the buffer stage s - 1 used (consumed)
-        if constexpr (R16_S16) {
-            r16_stage_s16<G, W, NS>(sbuf + (s % R16_RING) * STAGE_H8, bq, mn, lane);
+        if constexpr (CMP) {
+            r16_stage_s16k<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
+            r16_close_s16<G, W, NS>(s, tps, smin, mn, lane);
+        } else if constexpr (R16_S16) {
+            r16_stage_s16<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
             r16_close_s16<G, W, NS>(s, tps, smin, mn, lane);
         } else {
-            r16_stage<G, W, NS>(sbuf + (s % R16_RING) * STAGE_H8, bq, mn, lane);
+            r16_stage<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
             r16_close<G, W, NS>(s, tps, smin, mn, lane);
         }
         const int done = (s + 1) * STAGE_TILES;
@@ -413,7 +465,7 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
             }
         }
         // stage s + 1 landed: the R16_RING - 2 stages issued after it may stay in flight
-        if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(R16_MFMA * (R16_RING - 2)) : "memory");
+        if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (R16_RING - 2)) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         stage_barrier();   // (every wave's reads of stage s done: its buffer is refilled next)
     }
@@ -457,6 +509,39 @@ __global__ __launch_bounds__(256, IA_R16_OCC) void k_screen16r(const half8 *__re
     else if (wv == 1) r16_body<G, 1>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
     else if (wv == 2) r16_body<G, 2>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
     else r16_body<G, 3>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+}
+
+// the compact screen (ia_rot16.h RK_*; one job): k_screen16r's grid, parts and minima over the
+// compact DB (ia_db_build_rotk) and the compact operands of the same query rows
+template <int G>
+__global__ __launch_bounds__(256, IA_R16_OCC) void k_screen16c(const half8 *__restrict__ dbk, int nchunks, int ch,
+                                                      int seg_rows, StageMap sm,
+                                                      const half8 *__restrict__ q16, int M, int groups,
+                                                      float *__restrict__ segmin, long nseg, int split) {
+    __shared__ half8 sbuf[R16_RING * STAGE_TILES * RK_TILE_H8];
+    __shared__ int smin[SPC_STAGE * G * 32];
+    const int b = blockIdx.x;
+    const int slot = b >> 3;
+    const int part = (slot / groups) * 8 + (b & 7);
+    const int group = slot - (slot / groups) * groups;
+    if (part >= nchunks * split) return;   // uniform over the block, before any barrier
+    const int lsp = __builtin_ctz((unsigned)split);
+    const int chunk = part >> lsp, half = part & (split - 1);
+    const int spc = ch / seg_rows;
+    for (int i = threadIdx.x; i < SPC_STAGE * G * 32; i += 256) smin[i] = 0x7fffffff;
+    const int nstage = (ch / (STAGE_TILES * 32)) >> lsp;
+    const int tps = seg_rows >> 5;
+    const half8 *qg = q16 + (long)group * G * 32 * Q16_ROW;
+    const long seg0 = (long)chunk * spc + (long)half * (spc >> lsp);
+    const int q0 = group * G * 32;
+    const int s0 = half * nstage;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if constexpr (RK_BUILT) {
+        if (wv == 0) r16_body<G, 0, true>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+        else if (wv == 1) r16_body<G, 1, true>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+        else if (wv == 2) r16_body<G, 2, true>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+        else r16_body<G, 3, true>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+    }
 }
 
 // ---- the wave-owned form (IA_R16_FORM = 1): DB tiles straight into each wave's registers ----
@@ -670,6 +755,27 @@ __global__ __launch_bounds__(256) void k_db_cov_reduce(const double *__restrict_
 // ia_rot16.h in the tile layout (10 half8 stores), and the skipped components' norm for
 // amax[1] (A_skip, rounded up).  amax[0] (A, the split scale's bound) is computed first by
 // the same range / bound kernels as every other form (launch_db_amax).
+// rho = V^T d of one row (fp64 from the fp32 rotation R in LDS): f(j, rho_j), j = 0 .. 54 in order
+template <typename F>
+__device__ __forceinline__ void r16_rotate_row(const float *R, const double (&d)[IA_D], F &&f) {
+#pragma unroll
+    for (int jb = 0; jb < R16_LD; jb += 4) {
+        double k0 = 0.0, k1 = 0.0, k2 = 0.0, k3 = 0.0;
+#pragma unroll
+        for (int k = 0; k < IA_D; ++k) {
+            const float4 v = *reinterpret_cast<const float4 *>(&R[k * R16_LD + jb]);
+            k0 = fma((double)v.x, d[k], k0);
+            k1 = fma((double)v.y, d[k], k1);
+            k2 = fma((double)v.z, d[k], k2);
+            k3 = fma((double)v.w, d[k], k3);
+        }
+        const double kk[4] = {k0, k1, k2, k3};
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (jb + e < IA_D) f(jb + e, kk[e]);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_db_build_rot(DbSrc src, long row0, long nrows, long npad,
                                                       const double *__restrict__ center,
                                                       const float *__restrict__ rot, float *amax,
@@ -695,35 +801,19 @@ __global__ __launch_bounds__(256) void k_db_build_rot(DbSrc src, long row0, long
         const Split16Db sc = split16_db_scale(amax[0]);
         half8 o[2 * R16_MFMA];
         double sk = 0.0;
-#pragma unroll
-        for (int jb = 0; jb < R16_LD; jb += 4) {
-            double k0 = 0.0, k1 = 0.0, k2 = 0.0, k3 = 0.0;
-#pragma unroll
-            for (int k = 0; k < IA_D; ++k) {
-                const float4 v = *reinterpret_cast<const float4 *>(&R[k * R16_LD + jb]);
-                k0 = fma((double)v.x, d[k], k0);
-                k1 = fma((double)v.y, d[k], k1);
-                k2 = fma((double)v.z, d[k], k2);
-                k3 = fma((double)v.w, d[k], k3);
+        r16_rotate_row(R, d, [&](int j, double rho) {
+            const float r32 = (float)rho;
+            if (j >= R16_P) sk += (double)r32 * (double)r32;
+            _Float16 h, l;
+            split16f_sat(ldexpf(r32, sc.ea), h, l);
+            const int s = R16_M0 + j;
+            o[((s & 15) >> 3) * R16_MFMA + (s >> 4)][s & 7] = h;
+            if (j < R16_P) {
+                const int s0 = 2 * j, s1 = 2 * j + 1;
+                o[((s0 & 15) >> 3) * R16_MFMA + (s0 >> 4)][s0 & 7] = l;
+                o[((s1 & 15) >> 3) * R16_MFMA + (s1 >> 4)][s1 & 7] = h;
             }
-            const double kk[4] = {k0, k1, k2, k3};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int j = jb + e;
-                if (j >= IA_D) continue;
-                const float r32 = (float)kk[e];
-                if (j >= R16_P) sk += (double)r32 * (double)r32;
-                _Float16 h, l;
-                split16f_sat(ldexpf(r32, sc.ea), h, l);
-                const int s = R16_M0 + j;
-                o[((s & 15) >> 3) * R16_MFMA + (s >> 4)][s & 7] = h;
-                if (j < R16_P) {
-                    const int s0 = 2 * j, s1 = 2 * j + 1;
-                    o[((s0 & 15) >> 3) * R16_MFMA + (s0 >> 4)][s0 & 7] = l;
-                    o[((s1 & 15) >> 3) * R16_MFMA + (s1 >> 4)][s1 & 7] = h;
-                }
-            }
-        }
+        });
         _Float16 nh, nl;
         split16f_sat(ldexpf((float)n2, sc.ea - sc.R), nh, nl);
         o[((R16_NL & 15) >> 3) * R16_MFMA + (R16_NL >> 4)][R16_NL & 7] = nl;
@@ -753,13 +843,71 @@ __global__ __launch_bounds__(256) void k_db_build_rot(DbSrc src, long row0, long
     }
 }
 
+// the compact DB (ia_db_build_rotk, ia_rot16.h RK_*): as k_db_build_rot with amax[0] given: per
+// padded row the 32 compact slots (4 half8, one per lane quarter's group), the norm slots
+// from |rho_C|^2; |rho_rest| (components C..54 in fp64, rounded up) into the segment's R_j and Rmax
+__global__ __launch_bounds__(256) void k_db_build_rotk(DbSrc src, long row0, long nrows, long npad,
+                                                       const double *__restrict__ center,
+                                                       const float *__restrict__ rot, const float *__restrict__ amax,
+                                                       half8 *__restrict__ dbk, StageMap sm, int seg_rows,
+                                                       unsigned *__restrict__ rseg, unsigned *__restrict__ rmax) {
+    __shared__ __attribute__((aligned(16))) float R[R16_LD * R16_LD];
+    for (int i = threadIdx.x; i < R16_LD * R16_LD / 4; i += 256)
+        reinterpret_cast<float4 *>(R)[i] = reinterpret_cast<const float4 *>(rot)[i];
+    __syncthreads();
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    float rest = 0.f;
+    if (p < npad) {
+        const long r = row0 + (p < nrows ? p : nrows - 1);
+        double d[IA_D];
+        ImgPair ap; int rr, cc;
+        src.locate(r, ap, rr, cc);
+        emit_feature(src.A, ap, rr, cc, [&](int k, double v) { d[k] = v - center[k]; });
+        const Split16Db sc = split16_db_scale(amax[0]);
+        half8 o[RK_SLOTS / 8];
+        double nc = 0.0, nr = 0.0;
+        r16_rotate_row(R, d, [&](int j, double rho) {
+            if (j >= RK_C) {
+                nr += rho * rho;
+                return;
+            }
+            nc += rho * rho;
+            _Float16 h, l;
+            split16f_sat(ldexpf((float)rho, sc.ea), h, l);
+            o[(RK_M0 + j) >> 3][(RK_M0 + j) & 7] = h;
+            if (j < R16_P) {
+                o[(2 * j) >> 3][(2 * j) & 7] = l;
+                o[(2 * j + 1) >> 3][(2 * j + 1) & 7] = h;
+            }
+        });
+        _Float16 nh, nl;
+        split16f_sat(ldexpf((float)nc, sc.ea - sc.R), nh, nl);
+        o[RK_NL >> 3][RK_NL & 7] = nl;
+        o[RK_NH >> 3][RK_NH & 7] = nh;
+        half8 *t = dbk + (p >> 5) * RK_TILE_H8 + (p & 31);
+#pragma unroll
+        for (int g = 0; g < RK_SLOTS / 8; ++g) __builtin_nontemporal_store(o[g], t + g * 32);
+        const double a = sqrt(nr * (1.0 + 1e-12));
+        rest = (float)a;
+        if ((double)rest < a) rest = nextafterf(rest, INFINITY);
+    }
+    for (int o = 32; o > 0; o >>= 1) rest = fmaxf(rest, __shfl_xor(rest, o));
+    // (the wave's 64 rows lie in one segment; non-negative floats order like their bit patterns)
+    const long pw = p - (threadIdx.x & 63);
+    if ((threadIdx.x & 63) == 0 && pw < npad) {
+        atomicMax(rseg + seg_of_lrow(sm, pw, seg_rows), __float_as_uint(rest));
+        atomicMax(rmax, __float_as_uint(rest));
+    }
+}
+
 // per segment j the code c_j = ceil(255 A_skip,j / A_skip) (so A_skip c_j / 255 >= A_skip,j,
-// checked in fp64 and bumped), the exact stage's per-segment skip bound (r16_askc)
-__global__ __launch_bounds__(256) void k_askseg_codes(const float *__restrict__ askseg, const float *__restrict__ amax,
+// checked in fp64 and bumped), the exact stage's per-segment skip bound (r16_askc); gmax: the
+// maximum over the segments (A_skip; the compact DB's Rmax with its R_j)
+__global__ __launch_bounds__(256) void k_askseg_codes(const float *__restrict__ askseg, const float *__restrict__ gmax,
                                                       long nseg, unsigned char *__restrict__ codes) {
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j >= nseg) return;
-    const double ag = (double)amax[1], aj = (double)askseg[j];
+    const double ag = (double)gmax[0], aj = (double)askseg[j];
     int c = 0;
     if (ag > 0.0 && aj > 0.0) {
         c = (int)ceil(255.0 * aj / ag);
@@ -775,13 +923,13 @@ __global__ __launch_bounds__(64) void k_query_rows_r16(const double *__restrict_
                                                        const float *__restrict__ rot,
                                                        const float *__restrict__ amax,
                                                        double *__restrict__ nq, double *__restrict__ nsk,
-                                                       _Float16 *__restrict__ q16) {
+                                                       _Float16 *__restrict__ q16, bool compact) {
     __shared__ double dq[64];
     const int m = blockIdx.x, lane = threadIdx.x;
     const double d = lane < IA_D ? qin[(long)m * IA_DP + lane] - center[lane] : 0.0;
     double d2 = d * d;
     for (int o = 32; o > 0; o >>= 1) d2 += __shfl_xor(d2, o);
-    const double s2 = r16_write_query(q16 + (long)m * Q16_ROW * 8, lane, d, d2, amax[0], rot, dq);
+    const double s2 = r16_write_query(q16 + (long)m * Q16_ROW * 8, lane, d, d2, amax[0], rot, dq, compact);
     if (lane == 0) {
         nq[m] = d2;
         nsk[m] = s2;
@@ -799,7 +947,8 @@ static std::atomic<int> g_r16_form{env_int("IA_R16_FORM", 0)};
 static int r16_form() { return g_r16_form.load(std::memory_order_relaxed); }
 
 int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Float16 *q16, int M,
-                     float *segmin, hipStream_t st, const XJob *jobs, int njobs, int parity) {
+                     float *segmin, hipStream_t st, const XJob *jobs, int njobs, int parity, bool compact) {
+    IA_ARG(!compact || (RK_BUILT && njobs == 1 && !jobs), "launch_screen16r: the compact form takes one job");
     const int ch = db_chunk_rows(nrows);
     const long nchunks = db_nchunks(nrows);
     const int seg_rows = db_seg_rows(nrows);
@@ -839,7 +988,10 @@ int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Flo
     const dim3 gridw((unsigned)(((nsb + 7) / 8) * 8 * groups), (unsigned)njobs);
 #define IA_R16_CASE(GG)                                                                             \
     case GG:                                                                                        \
-        if (wform)                                                                                  \
+        if (compact)                                                                                \
+            k_screen16c<GG><<<grid, 256, 0, st>>>(db16, (int)nchunks, ch, seg_rows, sm, q, M,       \
+                                                  groups, segmin, nseg, split);                     \
+        else if (wform)                                                                             \
             k_screen16w<GG><<<gridw, 512, 0, st>>>(db16, (int)nsb, spb, tps, seg_rows, sm, q, M,    \
                                                    groups, segmin, nseg, jobs, parity);             \
         else                                                                                        \
@@ -866,8 +1018,9 @@ int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Flo
 }
 
 int launch_query_rows_r16(const double *q64, int M, const double *center, const float *rot,
-                          const float *amax, double *nq, double *nsk, _Float16 *q16, hipStream_t st) {
-    k_query_rows_r16<<<M, 64, 0, st>>>(q64, center, rot, amax, nq, nsk, q16);
+                          const float *amax, double *nq, double *nsk, _Float16 *q16, hipStream_t st,
+                          bool compact = false) {
+    k_query_rows_r16<<<M, 64, 0, st>>>(q64, center, rot, amax, nq, nsk, q16, compact);
     IA_LAUNCH_CHECK("k_query_rows_r16");
     return IA_OK;
 }
@@ -970,10 +1123,50 @@ int ia_db_build_rot(const IaSrcLevel *src, long row0, long nrows, const double *
                                                                   db_seg_rows(nrows), askseg);
     IA_LAUNCH_CHECK("k_db_build_rot");
     k_askseg_codes<<<(unsigned)((nseg + 255) / 256), 256, 0, st>>>(
-        reinterpret_cast<const float *>(askseg), amax, nseg,
+        reinterpret_cast<const float *>(askseg), amax + 1, nseg,
         reinterpret_cast<unsigned char *>(tail + r16_askc_off(nrows)));
     IA_LAUNCH_CHECK("k_askseg_codes");
     return db_check_amax(amax, st, "ia_db_build_rot");
+}
+
+size_t ia_db_rotk_bytes(long nrows) { return nrows > 0 && RK_BUILT ? rk_bytes(nrows) : 0; }
+
+int ia_db_rotk_applies(const IaSrcLevel *src, long row0, long nrows) {
+    // single-shard strip-order levels of the fused strip kernel at or above the row threshold
+    if (!RK_BUILT || !ia_db_rot_applies(src, row0, nrows) || nrows < compact_min_rows()) return 0;
+    if (row0 != 0 || nrows != (long)src->nAp * src->Ah * src->Aw) return 0;
+    const DbSrc d = make_dbsrc(*src);
+    return db_stage_map(row0, nrows, src->Aw, src->Ah).W > 0 && xstrip_applies(d) && db_seg_rows(nrows) >= 128 ? 1 : 0;
+}
+
+int ia_db_build_rotk(const IaSrcLevel *src, long row0, long nrows, const double *center, const float *rot,
+                     const float *amax, void *dbk, void *stream) {
+    IA_ARG(src && center && rot && amax && dbk && nrows > 0 && row0 >= 0, "ia_db_build_rotk: bad args");
+    IA_ARG(RK_BUILT, "ia_db_build_rotk: this build has no compact form");
+    IA_ARG(row0 + nrows <= (long)src->nAp * src->Ah * src->Aw, "ia_db_build_rotk: rows out of range");
+    IA_ARG(row0 + nrows < (1L << 31), "ia_db_build_rotk: rows past 2^31");
+    // (k_db_build_rotk's per-wave R_j: a wave's 64 rows lie in one segment; the compact waves' exact
+    // stage is the strip kernel's)
+    IA_ARG(db_seg_rows(nrows) % 64 == 0 && db_stage_map(row0, nrows, src->Aw, src->Ah).W > 0,
+           "ia_db_build_rotk: not a strip-order level (ia_db_rotk_applies)");
+    hipStream_t st = S(stream);
+    const DbSrc d = make_dbsrc(*src);
+    const long npad = db_rows_padded(nrows);
+    const StageMap sm = db_stage_map(row0, nrows, src->Aw, src->Ah);
+    const long nseg = db_nsegs(nrows);
+    char *base = reinterpret_cast<char *>(dbk);
+    unsigned *rseg = reinterpret_cast<unsigned *>(base + rk_rseg_off(nrows));
+    unsigned *rmax = reinterpret_cast<unsigned *>(base + rk_rmax_off(nrows));
+    IA_HIP(hipMemsetAsync(rseg, 0, rk_bytes(nrows) - rk_rseg_off(nrows), st));
+    k_db_build_rotk<<<(unsigned)((npad + 255) / 256), 256, 0, st>>>(d, row0, nrows, npad, center, rot, amax,
+                                                                   reinterpret_cast<half8 *>(dbk), sm,
+                                                                   db_seg_rows(nrows), rseg, rmax);
+    IA_LAUNCH_CHECK("k_db_build_rotk");
+    k_askseg_codes<<<(unsigned)((nseg + 255) / 256), 256, 0, st>>>(
+        reinterpret_cast<const float *>(rseg), reinterpret_cast<const float *>(rmax), nseg,
+        reinterpret_cast<unsigned char *>(base + rk_code_off(nrows)));
+    IA_LAUNCH_CHECK("k_askseg_codes");
+    return IA_OK;
 }
 
 /* diagnostics: one R16 screen of M fp64 query rows (IA_DP each) over a rotated DB ->
@@ -989,6 +1182,21 @@ int ia_diag_screen16r(const IaSrcLevel *src, long row0, long nrows, const void *
     if (rc) return rc;
     const StageMap sm = db_stage_map(row0, nrows, src->Aw, src->Ah);
     return launch_screen16r(dbr, nrows, sm, reinterpret_cast<const _Float16 *>(q16), M, segmin, st, nullptr, 1, 0);
+}
+
+/* the same with the compact screen over dbk (ia_db_build_rotk): segmin holds lower bounds
+ * only; |kappa_rest|^2 of query m is the double at byte 192 of its q16 row */
+int ia_diag_screen16k(const IaSrcLevel *src, long row0, long nrows, const void *dbk, const float *rot,
+                      const float *amax, const double *center, const double *q64, int M, void *q16,
+                      double *nq, double *nsk, float *segmin, void *stream) {
+    IA_ARG(src && dbk && rot && amax && center && q64 && q16 && nq && nsk && segmin && M > 0,
+           "ia_diag_screen16k: bad args");
+    hipStream_t st = S(stream);
+    int rc = launch_query_rows_r16(q64, M, center, rot, amax, nq, nsk, reinterpret_cast<_Float16 *>(q16), st, true);
+    if (rc) return rc;
+    const StageMap sm = db_stage_map(row0, nrows, src->Aw, src->Ah);
+    return launch_screen16r(dbk, nrows, sm, reinterpret_cast<const _Float16 *>(q16), M, segmin, st, nullptr, 1, 0,
+                            true);
 }
 
 }  // extern "C"

@@ -308,6 +308,13 @@ static void prof_push(const ProfRec &r) {
 static std::atomic<int> g_graph_mode{env_int("IA_GRAPH", 0)};
 static int graph_mode() { return g_graph_mode.load(std::memory_order_relaxed); }
 
+// the compact screen's level threshold (rows; DESIGN.md §4d: c4's finest level pays, measured);
+// LONG_MAX: off (ia_diag_set_compact_min_rows)
+static std::atomic<long> g_compact_min_rows{1L << 22};
+long compact_min_rows() { return g_compact_min_rows.load(std::memory_order_relaxed); }
+// compact waves enqueued by this process (ia_diag_compact_waves: the tests' proof that the form ran)
+static std::atomic<long> g_compact_waves{0};
+
 int xwave_attributes(int form, bool rot, hipFuncAttributes *at);
 int screen16_attributes(bool img, hipFuncAttributes *at);
 int screen_resources_r16(hipFuncAttributes *at);
@@ -594,8 +601,14 @@ struct LevelRun {
         hipEvent_t e1 = timed ? prof_event(ev0 + 3 * nscreen + 1) : nullptr;
         if (e0) IA_HIP(hipEventRecord(e0, sq));
         const StageMap sm = db_stage_map(a->row0, a->nrows, src.A.w, src.A.h);
+        const int form = !im ? XW_ROWS
+                       : (xwave_on() == 2 && sm.W > 0 && xstrip_applies(src)) ? XW_STRIP : XW_IMG;
+        // a compact wave (ia_rot16.h RK_*): the 32-slot screen and the lower-bound exact stage on
+        // the waves without a row-0 or column-0 pixel of one unsharded job's strip-form R16 level
+        const bool rk = r16 && a->dbk && K == 1 && !a->comm && form == XW_STRIP && a->nrows >= compact_min_rows();
+        const bool cmp = rk && wave_compact(W, t);
         if (r16) {
-            if ((rc = launch_screen16r(a->dbr, a->nrows, sm, q16s[b], M, segmin, sq, jt, K, b)))
+            if ((rc = launch_screen16r(cmp ? a->dbk : a->dbr, a->nrows, sm, q16s[b], M, segmin, sq, jt, K, b, cmp)))
                 return rc;
         } else if ((rc = launch_screen16(a->db, im ? &img : nullptr, a->nrows, sm, q16s[b], M, segmin, sq, jt,
                                          K, b, a->comm != nullptr))) {
@@ -632,9 +645,15 @@ struct LevelRun {
         x.trace = xw_trace(a->tag);
         x.rot = r16 ? a->rot : nullptr;
         x.askc = r16 ? r16_askc(a->dbr, a->nrows) : nullptr;
+        x.rk = rk ? 1 : 0;
+        if (cmp) {
+            g_compact_waves.fetch_add(1, std::memory_order_relaxed);
+            const char *dbk = reinterpret_cast<const char *>(a->dbk);
+            x.restc = reinterpret_cast<const unsigned char *>(dbk + rk_code_off(a->nrows));
+            x.rmax = reinterpret_cast<const float *>(dbk + rk_rmax_off(a->nrows));
+            x.q16 = q16s[b];
+        }
         const int R = M > y_lo_n + M_n - y_lo ? M : y_lo_n + M_n - y_lo;
-        const int form = !im ? XW_ROWS
-                       : (xwave_on() == 2 && sm.W > 0 && xstrip_applies(src)) ? XW_STRIP : XW_IMG;
         if ((rc = launch_xwave(x, R, form, sq, K))) return rc;
         if (timed) IA_HIP(hipEventRecord(prof_event(ev0 + 3 * nscreen + 2), sq));
         ++nscreen;
@@ -748,6 +767,10 @@ int ia_diag_set_xwave(int on) {
 }
 
 int ia_level_resources(const IaSynthArgs *a, int *out) {
+    // (compact waves, ia_rot16.h RK_*, are not reported: they run only without a comm, where no
+    // kernel waits for another rank; their k_xstrip<false, true, true> (159 VGPRs against 151, the
+    // same LDS and 3 workgroups per CU) and k_screen16c (less LDS and fewer VGPRs) fit wherever the
+    // forms reported here do)
     // the kernels this level launches per wave, decided as LevelRun::init / xw_wave decide:
     // out = {waiting kernel LDS bytes, VGPRs; screen LDS bytes, VGPRs} (the forward-progress
     // rule of DESIGN.md §7, per level: ADVICE r05)
@@ -808,6 +831,16 @@ int ia_diag_set_graph_mode(int mode) {
     const int prev = graph_mode();
     if (mode >= 0 && mode <= 2) g_graph_mode.store(mode);
     return prev;
+}
+
+int ia_diag_wave_compact(int W, int t) { return wave_compact(W, t) ? 1 : 0; }
+
+long ia_diag_compact_waves(void) { return g_compact_waves.load(std::memory_order_relaxed); }
+
+long ia_diag_set_compact_min_rows(long rows) {
+    const long prev = compact_min_rows();
+    if (rows >= 0) g_compact_min_rows.store(rows > 0 ? rows : LONG_MAX);
+    return prev == LONG_MAX ? 0 : prev;
 }
 
 int ia_release_thread_resources(void) {

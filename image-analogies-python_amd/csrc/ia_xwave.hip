@@ -317,7 +317,7 @@ __device__ __forceinline__ void xw_next_query(const XArgs &a, int i, int y, int 
     for (int o = 32; o > 0; o >>= 1) d2 += __shfl_xor(d2, o);   // same sum in every lane
     if (lane == 0) a.nqn[m] = d2;
     if (rotl) {
-        const double s2 = r16_write_query(a.q16n + (long)m * Q16_ROW * 8, lane, d, d2, amx, rotl, dq);
+        const double s2 = r16_write_query(a.q16n + (long)m * Q16_ROW * 8, lane, d, d2, amx, rotl, dq, a.rk != 0);
         if (lane == 0) a.q64n[(long)m * IA_DP + IA_D] = s2;
     } else {
         split16_write_query(a.q16n + (long)m * Q16_ROW * 8, lane, d, d2, amx);
@@ -1109,6 +1109,82 @@ __device__ __forceinline__ void seg3_select_codes(const float4 *sq4, const unsig
         }
     }
 }
+// Compact waves (ia_rot16.h RK_*): the minima are lower bounds only.  The seed segment (rescored
+// first; any segment is valid, the one with the least bound keeps the selection tight) is the
+// least fp32 key m - S max(0, k - Rs r)^2 with its index (the skip codes' small term left out:
+// one array less in registers); rv[j]: the rest-norm codes of the 4 segments of v[j].  The
+// selection takes every other segment with rk_take.
+struct RkKey {
+    float S, k, Rs;
+};
+__device__ __forceinline__ void rk_seed4(const float4 &x, unsigned r, int seg, const RkKey &q, float &kb, int &ki) {
+    const float m[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const float g = fmaxf(q.k - q.Rs * (float)((r >> (8 * b)) & 255u), 0.f);
+        const float key = m[b] - q.S * g * g;
+        if (key < kb) {
+            kb = key;
+            ki = seg + b;
+        }
+    }
+}
+template <int XR>
+__device__ __forceinline__ void seg3_wave_seed(const float4 *sq4, const unsigned *rc4, long n4, int t3,
+                                               const float4 (&v)[XR], const unsigned (&rv)[XR], const RkKey &q,
+                                               float &kb, int &ki) {
+    kb = FLT_MAX;
+    ki = 0;
+#pragma unroll
+    for (int j = 0; j < XR; ++j) rk_seed4(v[j], rv[j], 4 * (t3 + j * 192), q, kb, ki);
+    for (long i = t3 + (long)XR * 192; i < n4; i += 192) rk_seed4(sq4[i], rc4[i], (int)(4 * i), q, kb, ki);
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ok = __shfl_xor(kb, o);
+        const int oi = __shfl_xor(ki, o);
+        if (ok < kb || (ok == kb && oi < ki)) {
+            kb = ok;
+            ki = oi;
+        }
+    }
+}
+__device__ __forceinline__ unsigned rk_sel4(const float4 &x, unsigned c, unsigned r, int seg, int seed,
+                                            const RkSel &s) {
+    return (rk_take(s, x.x, c & 255u, r & 255u) && seg != seed ? 1u : 0u) |
+           (rk_take(s, x.y, (c >> 8) & 255u, (r >> 8) & 255u) && seg + 1 != seed ? 2u : 0u) |
+           (rk_take(s, x.z, (c >> 16) & 255u, (r >> 16) & 255u) && seg + 2 != seed ? 4u : 0u) |
+           (rk_take(s, x.w, c >> 24, r >> 24) && seg + 3 != seed ? 8u : 0u);
+}
+template <int XR>
+__device__ __forceinline__ void seg3_select_rk(const float4 *sq4, const unsigned *ac4, const unsigned *rc4, long n4,
+                                               int t3, const float4 (&v)[XR], const unsigned (&cv)[XR],
+                                               const unsigned (&rv)[XR], const RkSel &s, int seed, int *slist,
+                                               int *scount) {
+    unsigned long long m = 0;
+#pragma unroll
+    for (int j = 0; j < XR; ++j)
+        m |= (unsigned long long)rk_sel4(v[j], cv[j], rv[j], 4 * (t3 + j * 192), seed, s) << (4 * j);
+    if (m) {
+        int pos = atomicAdd(scount, __builtin_popcountll(m));
+        while (m) {
+            const int b = __builtin_ctzll(m);
+            m &= m - 1;
+            if (pos < RESCORE_SEGCAP) slist[pos] = 4 * (t3 + (b >> 2) * 192) + (b & 3);
+            ++pos;
+        }
+    }
+    for (long i = t3 + (long)XR * 192; i < n4; i += 192) {
+        unsigned mt = rk_sel4(sq4[i], ac4[i], rc4[i], (int)(4 * i), seed, s);
+        if (mt) {
+            int pos = atomicAdd(scount, __builtin_popcount(mt));
+            while (mt) {
+                const int b = __builtin_ctz(mt);
+                mt &= mt - 1;
+                if (pos < RESCORE_SEGCAP) slist[pos] = (int)(4 * i + b);
+                ++pos;
+            }
+        }
+    }
+}
 // a barrier of waves 0, 2 and 3 only (an LDS counter; wave 1 never takes part): generation g
 // releases when all three have arrived for the g-th time
 __device__ __forceinline__ void sync3(unsigned *cnt, unsigned g, int lane) {
@@ -1128,8 +1204,12 @@ __device__ __forceinline__ void sync3(unsigned *cnt, unsigned g, int lane) {
 #ifndef IA_XSTRIP_BREG
 #define IA_XSTRIP_BREG 2   // float4s of segment minima per thread in registers, batch form
 #endif
-template <bool BATCH, bool ROT>
+// CMP: a compact wave of an R16 level (ia_rot16.h RK_*): the screen's minima are lower bounds
+// only, so the segment with the least bound (the seed) is rescored first, U = its fp64 minimum,
+// and the segments whose bound is within U follow; the same rows' exact minimum either way
+template <bool BATCH, bool ROT, bool CMP = false>
 __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArgs a0) {
+    static_assert(!CMP || (ROT && !BATCH), "compact waves: one job of an R16 level");
     __shared__ __attribute__((aligned(16))) char sa_raw[BATCH ? sizeof(XArgs) : 16];
     XArgs &sa = *reinterpret_cast<XArgs *>(sa_raw);
     if constexpr (BATCH) {
@@ -1228,10 +1308,19 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
         constexpr int XR = BATCH ? IA_XSTRIP_BREG : XS_REG;
         float4 v[XR];
         unsigned sgc[XR];
+        unsigned rgc[CMP ? XR : 1];   // compact: the segments' rest-norm codes
         const unsigned *ac4 = ROT ? reinterpret_cast<const unsigned *>(a.askc.get()) : nullptr;
+        const unsigned *rc4 = CMP ? reinterpret_cast<const unsigned *>(a.restc.get()) : nullptr;
+        // compact: |kappa_rest|^2 of this query (its q16 row) and Rmax
+        const double nrest =
+            CMP ? *reinterpret_cast<const double *>(reinterpret_cast<const char *>(a.q16.get()) +
+                                                    (long)i * (Q16_ROW * 16) + RK_Q_REST_B)
+                : 0.0;
+        const float rmx = CMP ? a.rmax[0] : 0.f;
         if (wv != 1) {
             seg3_load(sq4, n4, t3, v);
-            if constexpr (ROT) seg3_load_codes(ac4, n4, t3, sgc);
+            if constexpr (CMP) seg3_load_codes(rc4, n4, t3, rgc);   // (the skip codes: with the selection)
+            else if constexpr (ROT) seg3_load_codes(ac4, n4, t3, sgc);
         }
         const int rr0 = y - 2 + lane / 5, rc0 = x - 2 + lane % 5;
         const bool cpos_ok = wv == 1 && lane < XW_NCOH && rr0 >= 0 && rc0 >= 0 && rc0 < W &&
@@ -1248,7 +1337,14 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
         if constexpr (ROT) Kd = r16_kseg(am, ask, nqq, nsk);
         if (wv != 1) {
             float ewv;
-            if constexpr (ROT) {
+            if constexpr (CMP) {
+                // the seed: this wave's least key and its segment (bis: free until the winners)
+                const Split16Db sc = split16_db_scale(am);
+                const RkKey kq{ldexpf(1.f, sc.ea + split16_q_scale(nqq, sc.R)), (float)sqrt(nrest), rmx / 255.f};
+                int ki;
+                seg3_wave_seed(sq4, rc4, n4, t3, v, rgc, kq, ewv, ki);
+                if (lane == 0) bis[wv] = ki;
+            } else if constexpr (ROT) {
                 float Kf = (float)Kd;
                 if ((double)Kf < Kd) Kf = nextafterf(Kf, INFINITY);
                 ewv = seg3_wave_umin(sq4, ac4, n4, t3, v, sgc, Kf);
@@ -1323,7 +1419,18 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
         }
         int ns = 0;
         bool full = false;
-        if (wv != 1) {
+        int seed = 0;   // compact: the segment rescored first
+        if constexpr (CMP) {
+            if (wv != 1) {
+                sync3(&bar3, 1, lane);   // the seed (waves 0, 2, 3)
+                float kb = redf[0];
+                long long kl = bis[0];
+                if (redf[2] < kb || (redf[2] == kb && bis[2] < kl)) { kb = redf[2]; kl = bis[2]; }
+                if (redf[3] < kb || (redf[3] == kb && bis[3] < kl)) { kb = redf[3]; kl = bis[3]; }
+                seed = kl >= 0 && kl < a.nseg ? (int)kl : 0;
+                xw_stamp(trace, 2);
+            }
+        } else if (wv != 1) {
             sync3(&bar3, 1, lane);   // e* (waves 0, 2, 3)
             const float emin = fminf(redf[0], fminf(redf[2], redf[3]));
             xw_stamp(trace, 2);
@@ -1396,44 +1503,39 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
         XsWin w{};
         XsFix fx;
         const int dr = wv == 0 ? 0 : wv - 1;   // DMA rank of waves 0, 2, 3
-        long nit = full ? a.nseg : ns;          // (wave 1: after the barrier below)
-        if (wv != 1 && nit > 0) {
-            w = xs_window(a, full ? 0 : slist[0]);
+        // (compact: the seed's windows first; the selection follows its rescore, before the loop)
+        long nit = CMP ? 0 : full ? a.nseg : ns;          // (wave 1: after the barrier below)
+        if (wv != 1 && (CMP || nit > 0)) {
+            w = xs_window(a, CMP ? seed : full ? 0 : slist[0]);
             xs_dma(w, src.A, win, dr, lane, fx);
         }
         if (wv == 1) {
             coherence();
-        } else if (nit > 0) {
+        } else if (CMP || nit > 0) {
             win_dma_wait();
             xs_fix(fx, win, 64 * dr + lane);
         }
+        if (CMP && tid == 0) bis[1] = seed;
         __syncthreads();   // the first windows complete; the selection visible to wave 1
         if (wv == 1) {
-            ns = scount;
-            full = sfull != 0;
-            nit = full ? a.nseg : ns;
-            if (nit > 0) w = xs_window(a, full ? 0 : slist[0]);
+            if constexpr (CMP) {
+                seed = (int)bis[1];
+                w = xs_window(a, seed);
+            } else {
+                ns = scount;
+                full = sfull != 0;
+                nit = full ? a.nseg : ns;
+                if (nit > 0) w = xs_window(a, full ? 0 : slist[0]);
+            }
         }
-        const long nscan = nit;
+        long nscan = nit;
         // segments after the first: their windows are loaded into registers while the one
         // before is rescored, and stored after its last read (one LDS window, no DMA wait)
+        // (compact: the seed is rescored before the loop; the list follows, every window through pre)
         XsPre pre;
         XsWin wn{};
-        for (long si = 0; si < nit; ++si) {
-            if (si > 0) {
-                __syncthreads();   // every row of the last segment is read before the stores
-                xs_pre_store(pre, win, tid);
-                w = wn;
-                __syncthreads();   // the windows are complete
-            }
-            if (si + 1 < nit) {
-                wn = xs_window(a, full ? si + 1 : slist[si + 1]);
-                xs_pre_load(wn, src.A, tid, pre);
-            }
-            if (si == 0) {
-                xw_stamp(trace, 4);
-                if (wv == 0) wstamp(11);
-            }
+        // every row of the segment in the windows (w) against the query: the thread's best
+        auto rescore_rows = [&]() {
             const double *wdb = reinterpret_cast<const double *>(win);
             if (w.nst == 4) {
                 // 512 rows: thread tid takes pixels (y0 + 2p, x) and (y0 + 2p + 1, x),
@@ -1456,7 +1558,57 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
                 if (tid < a.seg_rows) fin_best(bd, bi, d0, w.g0 + (long)(k0 >> 7) * Aw + (k0 & 127));
                 if (tid + 256 < a.seg_rows) fin_best(bd, bi, d1, w.g0 + (long)(k1 >> 7) * Aw + (k1 & 127));
             }
-            if (si == 0 && wv == 0) wstamp(12);
+        };
+        if constexpr (CMP) {
+            xw_stamp(trace, 4);
+            if (wv == 0) wstamp(11);
+            rescore_rows();   // the seed
+            if (wv == 0) wstamp(12);
+            // U = the seed's exact minimum (bds: free until the winners), then the
+            // selection by waves 0, 2, 3 from the minima loaded again (L2), and the first
+            // listed segment's windows
+            double um = bd;
+            for (int o = 32; o > 0; o >>= 1) um = fmin(um, __shfl_xor(um, o));
+            if (lane == 0) bds[wv] = um;
+            if (wv != 1) {
+                seg3_load(sq4, n4, t3, v);
+                seg3_load_codes(ac4, n4, t3, sgc);
+                seg3_load_codes(rc4, n4, t3, rgc);
+            }
+            __syncthreads();
+            const double U = fmin(fmin(bds[0], bds[1]), fmin(bds[2], bds[3]));
+            bool force_full;
+            const RkSel sel = rk_select(U, am, ask, rmx, nqq, nsk, nrest, force_full);
+            if (wv != 1) seg3_select_rk(sq4, ac4, rc4, n4, t3, v, sgc, rgc, sel, seed, slist, &scount);
+            __syncthreads();
+            xw_stamp(trace, 3);
+            ns = scount;
+            full = ns > RESCORE_SEGCAP || force_full;
+            nit = full ? a.nseg : ns;
+            nscan = nit + 1;
+            if (trace && tid == 0) trace[XW_TRACE_N - 1] = (unsigned long long)nscan;
+            if (nit > 0) {
+                wn = xs_window(a, full ? 0 : slist[0]);
+                xs_pre_load(wn, src.A, tid, pre);
+            }
+        }
+        for (long si = 0; si < nit; ++si) {
+            if (si > 0 || CMP) {
+                __syncthreads();   // every row of the last segment is read before the stores
+                xs_pre_store(pre, win, tid);
+                w = wn;
+                __syncthreads();   // the windows are complete
+            }
+            if (si + 1 < nit) {
+                wn = xs_window(a, full ? si + 1 : slist[si + 1]);
+                xs_pre_load(wn, src.A, tid, pre);
+            }
+            if (!CMP && si == 0) {
+                xw_stamp(trace, 4);
+                if (wv == 0) wstamp(11);
+            }
+            rescore_rows();
+            if (!CMP && si == 0 && wv == 0) wstamp(12);
         }
         for (int o = 32; o > 0; o >>= 1) {
             const double od = __shfl_xor(bd, o);
@@ -1550,8 +1702,12 @@ int launch_xwave(const XArgs &a, int nblocks, int form, hipStream_t st, int njob
            "launch_xwave: the strip form needs a strip-order image-form level");
     const dim3 grid((unsigned)nblocks, (unsigned)njobs);
     const bool b = njobs > 1;
+    IA_ARG(!a.restc || (RK_BUILT && form == XW_STRIP && a.rot && !b && a.rmax && a.q16),
+           "launch_xwave: a compact wave is one job of an R16 strip level");
     if (form == XW_STRIP) {
-        if (a.rot) {
+        if (a.restc) {
+            k_xstrip<false, true, true><<<grid, 256, 0, st>>>(a);
+        } else if (a.rot) {
             if (b) k_xstrip<true, true><<<grid, 256, 0, st>>>(a);
             else k_xstrip<false, true><<<grid, 256, 0, st>>>(a);
         } else {

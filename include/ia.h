@@ -217,6 +217,16 @@ int ia_db_cov(const IaSrcLevel *src, long row0, long nrows, const double *center
               void *stream);
 int ia_db_build_rot(const IaSrcLevel *src, long row0, long nrows, const double *center,
                     const float *rot, float *amax, void *dbr, void *stream);
+/* The compact rotated database (DESIGN.md §4d "compact"): the leading 24 components only, 32
+ * K-slots = 64 B per padded row in ia_db_build_rot's order and segments, then per segment the
+ * largest norm R_j of the dropped components (fp32, rounded up), a byte r_j with Rmax r_j / 255
+ * >= R_j, and Rmax; ia_db_rotk_bytes in all (0: this build has no compact form).  Built after
+ * ia_db_build_rot with the same rot and amax (read only).  ia_db_rotk_applies: 1 for a whole
+ * (unsharded) strip-order level of the fused strip kernel with at least the threshold's rows. */
+size_t ia_db_rotk_bytes(long nrows);
+int ia_db_rotk_applies(const IaSrcLevel *src, long row0, long nrows);
+int ia_db_build_rotk(const IaSrcLevel *src, long row0, long nrows, const double *center,
+                     const float *rot, const float *amax, void *dbk, void *stream);
 
 /* ---- 3-channel matching (config.py:29-42 num_ch = 3: convert=False on colour images) ----
  * Images are h x w x 3 fp64, channel-interleaved; IaSrcLevel / IaSynthArgs keep their
@@ -292,6 +302,11 @@ typedef struct {
      * takes its bound; amax must then hold 2 floats {A, A_skip}.  Same results. */
     const void *dbr;
     const float *rot;
+    /* NULL, or with dbr the level's compact rotated database (ia_db_build_rotk): the waves
+     * without a row-0 or column-0 pixel of an unsharded strip-order level then screen its 64-B
+     * rows (one MFMA per 16 x 16 block) and the exact stage takes their lower bounds.  Same
+     * results. */
+    const void *dbk;
 } IaSynthArgs;
 /* the resources of ia_screen_resources / ia_fused_resources per level, from its IaSynthArgs as ia_synth_level would run it (the fused
  * kernel's form k_xstrip / k_xwave image / rows, or k_peer_finish without the fused kernel,

@@ -45,6 +45,19 @@ int ia_diag_screen16_image(const IaSrcLevel *src, long row0, long nrows, const v
 int ia_diag_screen16r(const IaSrcLevel *src, long row0, long nrows, const void *dbr, const float *rot,
                       const float *amax, const double *center, const double *q64, int M, void *q16,
                       double *nq, double *nsk, float *segmin, void *stream);
+/* the same over the compact rotated DB (ia_db_build_rotk) with the compact screen: segmin holds
+ * lower bounds of the segments' minima only (ia_rot16.h RK_*); |kappa_rest|^2 of query m is the
+ * double at byte 192 of its q16 row */
+int ia_diag_screen16k(const IaSrcLevel *src, long row0, long nrows, const void *dbk, const float *rot,
+                      const float *amax, const double *center, const double *q64, int M, void *q16,
+                      double *nq, double *nsk, float *segmin, void *stream);
+/* the compact form's level threshold for this process: levels of at least `rows` rows build and
+ * use it (ia_db_rotk_applies, ia_synth_level); 0 turns it off, negative leaves it; returns the
+ * previous value (0: off).  ia_diag_wave_compact: 1 iff wave t of a level W wide may take it. */
+long ia_diag_set_compact_min_rows(long rows);
+int ia_diag_wave_compact(int W, int t);
+/* compact waves (compact screen + compact exact stage) enqueued by this process so far */
+long ia_diag_compact_waves(void);
 /* exact stage form for this process: 0 one workgroup per query (k_rescore), 1 the work list
  * (k_select / k_items / k_gather), -1 the default (work list above 2^20 rows); other values
  * leave it; returns the previous value */
