@@ -200,6 +200,9 @@ _SIGS = {
     'ia_diag_set_compact_min_rows': (ctypes.c_long, [ctypes.c_long]),
     'ia_diag_wave_compact': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     'ia_diag_compact_waves': (ctypes.c_long, []),
+    'ia_diag_set_xsplit_min_rows': (ctypes.c_long, [ctypes.c_long]),
+    'ia_diag_xsplit_grid': (ctypes.c_int, [ctypes.c_int, ctypes.c_long, ctypes.c_int]),
+    'ia_diag_xsplit_counts': (ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
     'ia_diag_wave_rows': (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]),
     'ia_diag_pipe_schedule': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3 + [ctypes.c_int] * 3 +
                               [ctypes.POINTER(ctypes.c_int), ctypes.c_int]),

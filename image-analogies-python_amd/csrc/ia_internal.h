@@ -301,6 +301,9 @@ struct XArgs {
     gptr<const unsigned char> restc;
     gptr<const float> rmax;
     gptr<const _Float16> q16;
+    // split candidates (k_xstrip<false, true, CMP, true>; nullable otherwise): the helpers' records,
+    // 8 tagged granules per image row; the launch then has two workgroups per pixel
+    gptr<unsigned long long> xbox;
 };
 // k_xwave phase stamps (IA_XW_TRACE=<level tag>, ia_diag_xwave_trace): s_memrealtime (100
 // MHz) at XW_TRACE_N - 1 points of the pixels with ticket < XW_TRACE_PX of waves < XW_TRACE_T;
@@ -346,6 +349,8 @@ int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Flo
                      bool compact = false);
 // the compact form's row threshold (ia_diag_set_compact_min_rows; LONG_MAX: off)
 long compact_min_rows();
+// the split tail's row threshold (ia_diag_set_xsplit_min_rows; LONG_MAX: off)
+long xsplit_min_rows();
 // amax = max(amax, the split scale's bound of a level's four value ranges) (ia_features.hip);
 // part: DBB_BLOCKS x 8 doubles of scratch
 int launch_db_amax(const IaSrcLevel *src, const DbSrc &d, const double *center, float *amax,

@@ -187,6 +187,7 @@ struct SynthWs {
     unsigned long long *dbox;
     unsigned int *ctl;
     XJob *jtab;              // a batch's job table (ia_synth_levels_batch, job 0's workspace)
+    unsigned long long *xbox;   // split candidates: the helpers' records, 8 granules per row
 };
 constexpr int XW_CTL_ERR = 2;
 
@@ -213,6 +214,7 @@ static size_t carve(SynthWs *ws, char *base, int H, int W, long nrows, int nrank
     w.dbox = (unsigned long long *)take((size_t)H * 2 * sizeof(unsigned long long));
     w.ctl = (unsigned int *)take(256);
     w.jtab = (XJob *)take((size_t)IA_BATCH_MAX * sizeof(XJob));
+    w.xbox = (unsigned long long *)take((size_t)H * 8 * sizeof(unsigned long long));
     if (ws) *ws = w;
     return off;
 }
@@ -314,6 +316,21 @@ static std::atomic<long> g_compact_min_rows{1L << 22};
 long compact_min_rows() { return g_compact_min_rows.load(std::memory_order_relaxed); }
 // compact waves enqueued by this process (ia_diag_compact_waves: the tests' proof that the form ran)
 static std::atomic<long> g_compact_waves{0};
+// the split tail's level threshold (rows; DESIGN.md §6b "split": a pixel's candidate segments over
+// two workgroups of k_xstrip); LONG_MAX: off (ia_diag_set_xsplit_min_rows).  2^22 rows, as the
+// compact form: c4's finest level, 1.5-1.7 % of the step on two boxes; 2^20 measured no better
+// (profiles/xsplit_ab.txt).  IA_XSPLIT_MIN_ROWS: the process's initial threshold (0: off)
+static long xsplit_initial() {
+    const int v = env_int("IA_XSPLIT_MIN_ROWS", 1 << 22);
+    return v > 0 ? v : LONG_MAX;
+}
+static std::atomic<long> g_xsplit_min_rows{xsplit_initial()};
+long xsplit_min_rows() { return g_xsplit_min_rows.load(std::memory_order_relaxed); }
+// workgroups of the fused kernel's launch for R pixel rows: two per pixel where the split applies
+// (eligible: one unsharded job's strip-form R16 level), else one
+static int xsplit_grid(bool eligible, long nrows, int R) {
+    return eligible && nrows >= xsplit_min_rows() && db_nsegs(nrows) <= (1L << 20) ? 2 * R : R;
+}
 
 int xwave_attributes(int form, bool rot, hipFuncAttributes *at);
 int screen16_attributes(bool img, hipFuncAttributes *at);
@@ -439,6 +456,7 @@ struct LevelRun {
             IA_HIP(hipMemsetAsync(ws.qpb, 0, (size_t)qrows_alloc(Mmax) * IA_DP * sizeof(float), st));
             IA_HIP(hipMemsetAsync(ws.q16b, 0, (size_t)qrows_alloc(Mmax) * Q16_ROW * 16, st));
             IA_HIP(hipMemsetAsync(ws.dbox, 0, (size_t)H * 2 * sizeof(unsigned long long), st));
+            IA_HIP(hipMemsetAsync(ws.xbox, 0, (size_t)H * 8 * sizeof(unsigned long long), st));
         }
         return IA_OK;
     }
@@ -654,7 +672,9 @@ struct LevelRun {
             x.q16 = q16s[b];
         }
         const int R = M > y_lo_n + M_n - y_lo ? M : y_lo_n + M_n - y_lo;
-        if ((rc = launch_xwave(x, R, form, sq, K))) return rc;
+        const int nwg = xsplit_grid(r16 && K == 1 && !a->comm && form == XW_STRIP, a->nrows, R);
+        if (nwg != R) x.xbox = ws.xbox;
+        if ((rc = launch_xwave(x, nwg, form, sq, K))) return rc;
         if (timed) IA_HIP(hipEventRecord(prof_event(ev0 + 3 * nscreen + 2), sq));
         ++nscreen;
         pairs += (double)M * (double)a->nrows * K;
@@ -770,7 +790,8 @@ int ia_level_resources(const IaSynthArgs *a, int *out) {
     // (compact waves, ia_rot16.h RK_*, are not reported: they run only without a comm, where no
     // kernel waits for another rank; their k_xstrip<false, true, true> (159 VGPRs against 151, the
     // same LDS and 3 workgroups per CU) and k_screen16c (less LDS and fewer VGPRs) fit wherever the
-    // forms reported here do)
+    // forms reported here do; nor is the split tail, k_xstrip<false, true, CMP, true>: 155 / 161
+    // VGPRs, the same LDS and 3 workgroups per CU, also unsharded levels only)
     // the kernels this level launches per wave, decided as LevelRun::init / xw_wave decide:
     // out = {waiting kernel LDS bytes, VGPRs; screen LDS bytes, VGPRs} (the forward-progress
     // rule of DESIGN.md §7, per level: ADVICE r05)
@@ -842,6 +863,14 @@ long ia_diag_set_compact_min_rows(long rows) {
     if (rows >= 0) g_compact_min_rows.store(rows > 0 ? rows : LONG_MAX);
     return prev == LONG_MAX ? 0 : prev;
 }
+
+long ia_diag_set_xsplit_min_rows(long rows) {
+    const long prev = xsplit_min_rows();
+    if (rows >= 0) g_xsplit_min_rows.store(rows > 0 ? rows : LONG_MAX);
+    return prev == LONG_MAX ? 0 : prev;
+}
+
+int ia_diag_xsplit_grid(int eligible, long nrows, int R) { return xsplit_grid(eligible != 0, nrows, R); }
 
 int ia_release_thread_resources(void) {
     IA_HIP(g_graphs.retire());

@@ -1207,9 +1207,44 @@ __device__ __forceinline__ void sync3(unsigned *cnt, unsigned g, int lane) {
 // CMP: a compact wave of an R16 level (ia_rot16.h RK_*): the screen's minima are lower bounds
 // only, so the segment with the least bound (the seed) is rescored first, U = its fp64 minimum,
 // and the segments whose bound is within U follow; the same rows' exact minimum either way
-template <bool BATCH, bool ROT, bool CMP = false>
+// SPLIT: a pixel's candidate segments over two workgroups (DESIGN.md §6b "split"): the launch
+// has two workgroups per pixel, ticket tau -> pixel tau >> 1, role tau & 1 (0 the helper, 1 the
+// owner).  Both run the same phase 1 on the same inputs and so hold the same candidate set; the
+// segments are ranked by segment number (xs_rank) and the ranks fix the shares (xs_helpers;
+// compact: both rescore the seed).  The helper reduces its share to one XRec and
+// publishes it as 8 tagged granules (a.xbox, 8 per image row, tag t + 1); it never waits and does
+// nothing else (no coherence, tail, next query, stamps or statistics).  The owner merges that
+// record (xrec_take: commutative) after its own share, polling the granules only when the
+// helper's share is not empty (ns >= XS_SHARE_MIN and no full scan: that is the owner's alone).  It
+// waits for a lower ticket that never waits: the forward-progress rule of the header holds.
+constexpr int XS_RANK_SH = 20;                          // slist entry: segment | rank << 20
+constexpr int XS_SEG_MASK = (1 << XS_RANK_SH) - 1;      // (the host applies the split below 2^20 segments)
+__device__ unsigned long long g_xsplit_cnt[2];   // ia_diag_xsplit_counts
+// the helper's share of a list of ranked segments: the odd ranks (the shares differ by at most
+// one; lists of fewer than XS_SHARE_MIN segments are the owner's alone).  Measured against one or
+// two segments fewer for the helper, whose record reaches the owner one exchange after its last
+// segment: the even split was the better one (DESIGN.md §6b "split")
+constexpr int XS_SHARE_MIN = 2;
+__device__ __forceinline__ bool xs_helpers(int rank) { return rank & 1; }
+
+// rank of every listed segment among the list's segment numbers (distinct), into the entry's high
+// bits; thread t of nt takes entries t, t + nt, ...  The list's order is the selection's atomic
+// order; the ranks are a function of the set alone.  Entries are read masked while others are
+// ranked (whole-word LDS accesses: the low bits never change).  The caller's barrier follows.
+__device__ __forceinline__ void xs_rank(int *slist, int ns, int t, int nt) {
+    for (int k = t; k < ns; k += nt) {
+        const int s = __hip_atomic_load(&slist[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & XS_SEG_MASK;
+        int r = 0;
+        for (int j = 0; j < ns; ++j)
+            r += (__hip_atomic_load(&slist[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & XS_SEG_MASK) < s ? 1 : 0;
+        __hip_atomic_store(&slist[k], s | (r << XS_RANK_SH), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+
+template <bool BATCH, bool ROT, bool CMP = false, bool SPLIT = false>
 __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArgs a0) {
     static_assert(!CMP || (ROT && !BATCH), "compact waves: one job of an R16 level");
+    static_assert(!SPLIT || (ROT && !BATCH), "split candidates: one job of an R16 level");
     __shared__ __attribute__((aligned(16))) char sa_raw[BATCH ? sizeof(XArgs) : 16];
     XArgs &sa = *reinterpret_cast<XArgs *>(sa_raw);
     if constexpr (BATCH) {
@@ -1261,23 +1296,26 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
         scount = 0;
     }
     __syncthreads();
-    const int i = tk;
+    const int tau = tk;
+    const int i = SPLIT ? tau >> 1 : tau;
+    const bool helper = SPLIT && !(tau & 1);
     unsigned long long *trace =
-        (a.trace && i < XW_TRACE_PX && t < XW_TRACE_T) ? a.trace + ((long)t * XW_TRACE_PX + i) * XW_TRACE_N : nullptr;
+        (!helper && a.trace && i < XW_TRACE_PX && t < XW_TRACE_T) ? a.trace + ((long)t * XW_TRACE_PX + i) * XW_TRACE_N : nullptr;
     auto wstamp = [&](int k) {   // lane 0 of any wave
         if (trace && lane == 0) trace[k] = __builtin_amdgcn_s_memrealtime();
     };
     if (trace && tid == 0) trace[0] = t_start;
     xw_stamp(trace, 1);
-    if (i == 0 && tid == 0) __hip_atomic_store(&a.tickets[(t + 1) & 1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tau == 0 && tid == 0) __hip_atomic_store(&a.tickets[(t + 1) & 1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int y = f.y_lo + i, x = t - 3 * y;
     const bool cur = i < a.M;
     const bool nxt = y >= a.y_lo_n && y < a.y_lo_n + a.M_n;
+    if (helper && !cur) return;   // (no pixel of wave t: nothing to share)
 
     // wave 0: the next query's features that do not depend on wave t (as k_xwave)
     const float amx = a.amax[vidx(0)];
     int pdep = 0;
-    if (wv == 0 && nxt) {
+    if (wv == 0 && nxt && !helper) {
         int rr = 0, cc = 0;
         // (B and B' share their dimensions: feat_addr_v, no argument loads before the copies)
         const double *p = feat_addr_v(a.B.sm, a.B.lg, a.Bp.sm, a.Bp.lg, a.B.h, a.B.w, a.B.hs, a.B.ws, y, x + 1,
@@ -1360,7 +1398,7 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
         // transposed through LDS and picked after the selection, while waves 0, 2, 3 copy
         // the first windows
         double cv[XW_NCOH], cvl = 0.0;
-        if (wv == 1) {
+        if (wv == 1 && !helper) {
             int sr = s_r + y - rr0, sc = s_c + x - rc0;
             const bool ok = cpos_ok && sr >= 0 && sr < src.A.h && sc >= 0 && sc < src.A.w;
             sr = ok ? sr : 0;
@@ -1449,6 +1487,12 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
             full = ns > RESCORE_SEGCAP || force_full;
             if (tid == 0) sfull = full ? 1 : 0;
             if (trace && tid == 0) trace[XW_TRACE_N - 1] = (unsigned long long)(full ? a.nseg : ns);
+            if constexpr (SPLIT) {
+                if (!full && ns >= XS_SHARE_MIN) {   // the shares (waves 0, 2, 3; wave 1 reads them after the barrier)
+                    xs_rank(slist, ns, t3, 192);
+                    sync3(&bar3, 3, lane);
+                }
+            }
         }
 
         auto coherence = [&]() {
@@ -1505,13 +1549,28 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
         const int dr = wv == 0 ? 0 : wv - 1;   // DMA rank of waves 0, 2, 3
         // (compact: the seed's windows first; the selection follows its rescore, before the loop)
         long nit = CMP ? 0 : full ? a.nseg : ns;          // (wave 1: after the barrier below)
-        if (wv != 1 && (CMP || nit > 0)) {
-            w = xs_window(a, CMP ? seed : full ? 0 : slist[0]);
+        // SPLIT: this workgroup's entries of the list by their ranks (xs_helpers; an unranked list,
+        // ns < XS_SHARE_MIN, is the owner's); a full scan is the owner's alone
+        auto mine_from = [&](long k) {   // the first entry >= k of this workgroup's share (nit: none)
+            if constexpr (SPLIT) {
+                if (!full)
+                    while (k < nit && xs_helpers(slist[k] >> XS_RANK_SH) != helper) ++k;
+            }
+            return k;
+        };
+        auto seg_of = [&](long k) -> long {
+            if constexpr (SPLIT) return full ? k : (long)(slist[k] & XS_SEG_MASK);
+            else return full ? k : (long)slist[k];
+        };
+        if (helper && full) nit = 0;
+        long si0 = CMP ? 0 : mine_from(0);
+        if (wv != 1 && (CMP || si0 < nit)) {
+            w = xs_window(a, CMP ? seed : seg_of(si0));
             xs_dma(w, src.A, win, dr, lane, fx);
         }
         if (wv == 1) {
-            coherence();
-        } else if (CMP || nit > 0) {
+            if (!helper) coherence();
+        } else if (CMP || si0 < nit) {
             win_dma_wait();
             xs_fix(fx, win, 64 * dr + lane);
         }
@@ -1525,8 +1584,13 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
                 ns = scount;
                 full = sfull != 0;
                 nit = full ? a.nseg : ns;
-                if (nit > 0) w = xs_window(a, full ? 0 : slist[0]);
+                if (helper && full) nit = 0;
+                si0 = mine_from(0);
+                if (si0 < nit) w = xs_window(a, seg_of(si0));
             }
+        }
+        if constexpr (SPLIT && !CMP) {
+            if (helper && (full || ns < XS_SHARE_MIN)) return;   // an empty share: nothing is published
         }
         long nscan = nit;
         // segments after the first: their windows are loaded into registers while the one
@@ -1587,28 +1651,39 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
             nit = full ? a.nseg : ns;
             nscan = nit + 1;
             if (trace && tid == 0) trace[XW_TRACE_N - 1] = (unsigned long long)nscan;
-            if (nit > 0) {
-                wn = xs_window(a, full ? 0 : slist[0]);
+            if constexpr (SPLIT) {
+                if (helper && (full || ns < XS_SHARE_MIN)) return;   // an empty share: nothing is published
+                if (!full && ns >= XS_SHARE_MIN) {
+                    xs_rank(slist, ns, tid, 256);
+                    __syncthreads();
+                }
+            }
+            si0 = mine_from(0);
+            if (si0 < nit) {
+                wn = xs_window(a, seg_of(si0));
                 xs_pre_load(wn, src.A, tid, pre);
             }
         }
-        for (long si = 0; si < nit; ++si) {
-            if (si > 0 || CMP) {
+        for (long si = si0; si < nit;) {
+            const bool first = si == si0;
+            const long sn = mine_from(si + 1);
+            if (!first || CMP) {
                 __syncthreads();   // every row of the last segment is read before the stores
                 xs_pre_store(pre, win, tid);
                 w = wn;
                 __syncthreads();   // the windows are complete
             }
-            if (si + 1 < nit) {
-                wn = xs_window(a, full ? si + 1 : slist[si + 1]);
+            if (sn < nit) {
+                wn = xs_window(a, seg_of(sn));
                 xs_pre_load(wn, src.A, tid, pre);
             }
-            if (!CMP && si == 0) {
+            if (!CMP && first) {
                 xw_stamp(trace, 4);
                 if (wv == 0) wstamp(11);
             }
             rescore_rows();
-            if (!CMP && si == 0 && wv == 0) wstamp(12);
+            if (!CMP && first && wv == 0) wstamp(12);
+            si = sn;
         }
         for (int o = 32; o > 0; o >>= 1) {
             const double od = __shfl_xor(bd, o);
@@ -1652,11 +1727,53 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
         xw_stamp(trace, 5);
         if (wv != 0) return;
         if constexpr (ROT) {   // win is free: the rotation for the next query lands meanwhile
-            if (nxt) rot_dma();
+            if (nxt && !helper) rot_dma();
         }
         XRec lb{INFINITY, LLONG_MAX, 0.0, 0.0};
 #pragma unroll
         for (int k = 0; k < 4; ++k) xrec_take(lb, XRec{bds[k], bis[k], bwd[k], bvl[k]});
+        if constexpr (SPLIT) {
+            // lane k < 8: word k of the record {d, i, wd, val} (lo, hi each) in row y's granule k
+            unsigned long long *xb = a.xbox + 8 * (long)y + (lane & 7);
+            if (helper) {
+                const unsigned long long q = (lane & 6) == 0 ? (unsigned long long)__double_as_longlong(lb.d)
+                                           : (lane & 6) == 2 ? (unsigned long long)lb.i
+                                           : (lane & 6) == 4 ? (unsigned long long)__double_as_longlong(lb.wd)
+                                                             : (unsigned long long)__double_as_longlong(lb.val);
+                if (lane < 8)
+                    __hip_atomic_store(xb, dgran(t + 1, (unsigned int)(lane & 1 ? q >> 32 : q)), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+                if (lane == 0) atomicAdd(&g_xsplit_cnt[0], 1ULL);
+                return;
+            }
+            if (!full && ns >= XS_SHARE_MIN) {   // the helper's share is not empty: its record
+                unsigned long long g = 0;
+                bool dead = false;
+                const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+                for (;;) {
+                    g = __hip_atomic_load(xb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (__all((unsigned)(g >> 32) == (unsigned)(t + 1))) break;
+                    if (__builtin_amdgcn_s_memrealtime() - t0 > PEER_TIMEOUT_TICKS) {
+                        if (lane == 0) atomicOr(a.err, 1u);
+                        dead = true;
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(1);
+                }
+                if (a.stats && lane == 0)
+                    atomicAdd(&stats_slot(a.stats, i)[4], __builtin_amdgcn_s_memrealtime() - t0);
+                if (!dead) {
+                    auto word = [&](int k) {   // (lane k's payload, uniform)
+                        return ((unsigned long long)(unsigned)__shfl((int)(unsigned)g, k + 1) << 32) |
+                               (unsigned)__shfl((int)(unsigned)g, k);
+                    };
+                    const XRec hr{__longlong_as_double((long long)word(0)), (long long)word(2),
+                                  __longlong_as_double((long long)word(4)), __longlong_as_double((long long)word(6))};
+                    if (lane == 0 && (hr.d < lb.d || (hr.d == lb.d && hr.i < lb.i))) atomicAdd(&g_xsplit_cnt[1], 1ULL);
+                    xrec_take(lb, hr);
+                }
+            }
+        }
         xw_stamp(trace, 6);
         own = xw_finish(a, i, y, x, lane, lb, cs, csval, (unsigned int)(nscan * a.seg_rows), ns, full, trace);
     }
@@ -1682,6 +1799,14 @@ extern "C" int ia_fused_resources(int rot, int *lds, int *vgprs) {
     return IA_OK;
 }
 
+extern "C" int ia_diag_xsplit_counts(unsigned long long *out) {
+    IA_ARG(out, "ia_diag_xsplit_counts: bad args");
+    IA_HIP(hipDeviceSynchronize());
+    IA_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(ia::g_xsplit_cnt), 2 * sizeof(unsigned long long), 0,
+                               hipMemcpyDeviceToHost));
+    return IA_OK;
+}
+
 namespace ia {
 
 // the one-job fused kernel of a form (launch_xwave): k_xstrip<false, rot> (XW_STRIP),
@@ -1704,8 +1829,13 @@ int launch_xwave(const XArgs &a, int nblocks, int form, hipStream_t st, int njob
     const bool b = njobs > 1;
     IA_ARG(!a.restc || (RK_BUILT && form == XW_STRIP && a.rot && !b && a.rmax && a.q16),
            "launch_xwave: a compact wave is one job of an R16 strip level");
+    IA_ARG(!a.xbox || (form == XW_STRIP && a.rot && !b && !a.f.px.nranks && a.nseg <= XS_SEG_MASK + 1),
+           "launch_xwave: split candidates are for one unsharded job of an R16 strip level");
     if (form == XW_STRIP) {
-        if (a.restc) {
+        if (a.xbox) {   // nblocks = two workgroups per pixel (helper, owner)
+            if (a.restc) k_xstrip<false, true, true, true><<<grid, 256, 0, st>>>(a);
+            else k_xstrip<false, true, false, true><<<grid, 256, 0, st>>>(a);
+        } else if (a.restc) {
             k_xstrip<false, true, true><<<grid, 256, 0, st>>>(a);
         } else if (a.rot) {
             if (b) k_xstrip<true, true><<<grid, 256, 0, st>>>(a);

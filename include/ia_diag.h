@@ -58,6 +58,16 @@ long ia_diag_set_compact_min_rows(long rows);
 int ia_diag_wave_compact(int W, int t);
 /* compact waves (compact screen + compact exact stage) enqueued by this process so far */
 long ia_diag_compact_waves(void);
+/* the split tail (k_xstrip with a pixel's candidate segments over two workgroups)
+ * for this process: one unsharded job's strip-form R16 levels of at least `rows` rows launch two
+ * workgroups per pixel; 0 turns it off, negative leaves it; returns the previous value (0: off;
+ * initially IA_XSPLIT_MIN_ROWS, default 2^22).  ia_diag_xsplit_grid: the workgroups the fused kernel's launch
+ * has for R pixel rows of a level of nrows rows (eligible: one unsharded job's strip-form R16
+ * level).  ia_diag_xsplit_counts: since the process started, out[0] the pixels whose helper
+ * workgroup rescored at least one segment, out[1] the pixels whose winning record was the helper's. */
+long ia_diag_set_xsplit_min_rows(long rows);
+int ia_diag_xsplit_grid(int eligible, long nrows, int R);
+int ia_diag_xsplit_counts(unsigned long long *out);
 /* exact stage form for this process: 0 one workgroup per query (k_rescore), 1 the work list
  * (k_select / k_items / k_gather), -1 the default (work list above 2^20 rows); other values
  * leave it; returns the previous value */

@@ -127,6 +127,12 @@ def main():
         report('all captured queries', arr, rs)
         report('clean-wave queries (y>=1, x>=1)', arr[clean], rs)
         report('others (row 0 or column 0)', arr[~clean], rs)
+        if with_rest:
+            # the split tail (DESIGN.md §6b "split"): arr = 1 + n (the seed and the n listed
+            # segments); both workgroups rescore the seed, the slower one then ceil(n / 2) of the list
+            n = arr[clean] - 1
+            report('clean: 1 + n', 1 + n, rs)
+            report('clean: 1 + ceil(n / 2)', 1 + (n + 1) // 2, rs)
     print('total %.0f s' % (time.time() - t0))
 
 
