@@ -66,14 +66,21 @@ def free_port():
         return sk.getsockname()[1]
 
 
-def run_ranks(world, argv, timeout=100):
-    """Start `world` exchange_worker.py processes (gloo rendezvous, all on cuda:0)."""
+def run_ranks(world, argv, timeout=100, env=None):
+    """Start `world` exchange_worker.py processes (gloo rendezvous, all on cuda:0) and wait for
+    them, each at most `timeout` seconds (whatever still runs after a failed wait is killed).
+    env: variables on top of the ranks' environment (None removes one).  Returns the ranks'
+    outputs."""
     port = free_port()
     procs = []
+    extra = env or {}
     for r in range(world):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r),
                    MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), IA_TEST_DEVICE='0',
                    IA_SHARD_MIN_ROWS='0', IA_SHARE_GPU='1')
+        env.update({k: v for k, v in extra.items() if v is not None})
+        for k in [k for k, v in extra.items() if v is None]:
+            env.pop(k, None)
         procs.append(subprocess.Popen([sys.executable, '-u', os.path.join(HERE, 'exchange_worker.py')]
                                       + [str(a) for a in argv], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
@@ -88,6 +95,7 @@ def run_ranks(world, argv, timeout=100):
                 p.wait()
     for p, txt in zip(procs, outs):
         assert p.returncode == 0, txt[-3000:]
+    return outs
 
 
 @pytest.mark.parametrize('world,pipeline', [(2, 1), (3, 0)])

@@ -146,22 +146,25 @@ def queries_from(level, B_pyr, Bp_init, Bp_final):
     return np.hstack([o.level_features(B_pyr[level - 1], B_pyr[level], True), half])
 
 
-def tie_segments(rows, nn, order, seg):
+def tie_segments(rows, nn, order, seg, pool=None):
     """Per query: the number of segments (positions [j seg, (j + 1) seg) of `order`, the
     library's row order; positions past the last row repeat it, as the padding does) holding
-    a row bit-identical to the query's nearest neighbour rows[nn]."""
+    a row bit-identical to the query's nearest neighbour pool[nn].  pool: the rows nn indexes
+    (default: `rows` itself); with a shard's rows and the whole level as pool the count is 0
+    where the shard holds no copy of the level's nearest row."""
     N = len(rows)
     pos_row = np.minimum(np.asarray(order), N - 1)
     bits = np.ascontiguousarray(rows).view(np.uint64)
+    pbits = bits if pool is None else np.ascontiguousarray(pool).view(np.uint64)
     mult = np.random.RandomState(1).randint(1, 2 ** 62, rows.shape[1]).astype(np.uint64) * np.uint64(2) + np.uint64(1)
     with np.errstate(over='ignore'):
         h = (bits * mult).sum(axis=1, dtype=np.uint64)     # a 64-bit hash per row
-    count = {}
-    for j in np.unique(nn):
-        cand = np.flatnonzero(h == h[j])
-        same = np.zeros(N, dtype=bool)
-        same[cand[(bits[cand] == bits[j]).all(axis=1)]] = True
-        count[int(j)] = np.unique(np.flatnonzero(same[pos_row]) // seg).size
+        count = {}
+        for j in np.unique(nn):
+            cand = np.flatnonzero(h == (pbits[j] * mult).sum(dtype=np.uint64))
+            same = np.zeros(N, dtype=bool)
+            same[cand[(bits[cand] == pbits[j]).all(axis=1)]] = True
+            count[int(j)] = np.unique(np.flatnonzero(same[pos_row]) // seg).size
     return np.array([count[int(j)] for j in nn])
 
 
@@ -196,16 +199,29 @@ def app_reference(db, Q, s, im, shape, A_shape, w):
     return nn, sa, d.reshape(H, W)
 
 
-def segment_order(N, Ah, Aw):
-    """(order, seg): the matcher's segment order of an unsharded N-row level
-    (ia_diag_stage_map, host side only) and its segment length."""
+def segment_order(N, Ah, Aw, row0=0, nrows=None):
+    """(order, seg): the matcher's segment order of an N-row level, or of its shard of rows
+    [row0, row0 + nrows) as local rows (the chunk geometry is the shard's own:
+    ia_db_chunk_rows / ia_db_rows_padded of nrows, ia_diag_stage_map of the range; host side
+    only), and its segment length."""
     import _ia
     from test_gpu_split16 import _segment_order
     lib = _ia.lib()
-    npad = lib.ia_db_rows_padded(N)
-    seg = min(lib.ia_db_chunk_rows(N), 512)
-    idx = types.SimpleNamespace(row0=0, src=types.SimpleNamespace(Aw=Aw, Ah=Ah))
-    return _segment_order(idx, N, npad, seg), seg
+    nrows = N - row0 if nrows is None else nrows
+    npad = lib.ia_db_rows_padded(nrows)
+    seg = min(lib.ia_db_chunk_rows(nrows), 512)
+    idx = types.SimpleNamespace(row0=row0, src=types.SimpleNamespace(Aw=Aw, Ah=Ah))
+    return _segment_order(idx, nrows, npad, seg), seg
+
+
+def case_pyramids(images, cap, seed, bp_scale=None, setup=None):
+    """(A_pyr, Ap_list, B_pyr, Bp_pyr, L) of a case's images: o.setup_luminance, and the random
+    B' initialisation at the images' scale where the case has one."""
+    A, Aps, B = images
+    A_pyr, Ap_list, B_pyr, Bp_pyr, L = o.setup_luminance(A, Aps, B, cap=cap, seed=seed, **(setup or {}))
+    if bp_scale is not None:
+        Bp_pyr = [b * bp_scale for b in Bp_pyr]
+    return A_pyr, Ap_list, B_pyr, Bp_pyr, L
 
 
 class LumCase:
@@ -215,12 +231,8 @@ class LumCase:
     setup: further arguments of o.setup_luminance (AB_weight, remap_lum, init_rand)."""
 
     def __init__(self, images, cap, k, seed, tie=True, bp_scale=None, setup=None):
-        A, Aps, B = images
         self.k = k
-        A_pyr, Ap_list, B_pyr, Bp_pyr, L = o.setup_luminance(A, Aps, B, cap=cap, seed=seed, **(setup or {}))
-        if bp_scale is not None:        # the random B' initialisation at the images' scale
-            Bp_pyr = [b * bp_scale for b in Bp_pyr]
-        self.pyr = A_pyr, Ap_list, B_pyr, Bp_pyr, L
+        A_pyr, Ap_list, B_pyr, Bp_pyr, L = self.pyr = case_pyramids(images, cap, seed, bp_scale, setup)
         self.L = L
         self.w = o.compute_weights(3, 5, 12, 1)
         prev = oc.set_threads(0)
@@ -257,26 +269,30 @@ class LumCase:
 _CASES = {}
 
 
+def lum_spec(name):
+    """LumCase's arguments for a named case (the rank processes of test_gpu_shards.py build the
+    same pyramids from them with case_pyramids, without the oracle run)."""
+    if name == 'over':      # 589,824 rows, 1152 segments: flat queries tie over > 1024
+        return dict(images=label_inputs(90, (768, 768), (16, 48), 1, band=10, patch=96), cap=2, k=1.0, seed=90)
+    if name == 'at':        # 524,288 rows, exactly 1024 segments, every one tied
+        return dict(images=label_inputs(95, (512, 512), (16, 48), 2, band=0, patch=96, same_bg=True), cap=2,
+                    k=1.0, seed=95)
+    if name == 'padded':    # 156,672 rows = 306 chunks of 512 padded to 308: a linear level
+        return dict(images=label_inputs(97, (204, 768), (16, 48), 1, band=0, patch=96), cap=2, k=1.0, seed=97)
+    if name == 'plain':     # an ordinary job of the over-cap shapes (the batch's second job)
+        return dict(images=analogy_inputs(91, (768, 768), (16, 48), 1), cap=2, k=1.0, seed=91, tie=False)
+    kind, size = name.split('@')
+    shapes = {'small': ((40, 52), (24, 31), None), 'strip': ((256, 512), (12, 30), 1)}[size]
+    if kind == 'huge':      # (the finest level only: huge_inputs)
+        A, Aps, B, sc = huge_inputs(93, shapes[0], shapes[1])
+        return dict(images=(A, Aps, B), cap=1, k=1.0, seed=93, tie=False, bp_scale=sc)
+    return dict(images=degenerate_inputs(kind, 93, shapes[0], shapes[1]), cap=shapes[2], k=1.0, seed=93,
+                tie=False, bp_scale=1e-25 if kind == 'scaled' else None)
+
+
 def lum_case(name):
     if name not in _CASES:
-        if name == 'over':      # 589,824 rows, 1152 segments: flat queries tie over > 1024
-            c = LumCase(label_inputs(90, (768, 768), (16, 48), 1, band=10, patch=96), 2, 1.0, 90)
-        elif name == 'at':      # 524,288 rows, exactly 1024 segments, every one tied
-            c = LumCase(label_inputs(95, (512, 512), (16, 48), 2, band=0, patch=96, same_bg=True), 2, 1.0, 95)
-        elif name == 'padded':  # 156,672 rows = 306 chunks of 512 padded to 308: a linear level
-            c = LumCase(label_inputs(97, (204, 768), (16, 48), 1, band=0, patch=96), 2, 1.0, 97)
-        elif name == 'plain':   # an ordinary job of the over-cap shapes (the batch's second job)
-            c = LumCase(analogy_inputs(91, (768, 768), (16, 48), 1), 2, 1.0, 91, tie=False)
-        else:
-            kind, size = name.split('@')
-            shapes = {'small': ((40, 52), (24, 31), None), 'strip': ((256, 512), (12, 30), 1)}[size]
-            if kind == 'huge':      # (the finest level only: huge_inputs)
-                A, Aps, B, sc = huge_inputs(93, shapes[0], shapes[1])
-                c = LumCase((A, Aps, B), 1, 1.0, 93, tie=False, bp_scale=sc)
-            else:
-                c = LumCase(degenerate_inputs(kind, 93, shapes[0], shapes[1]), shapes[2], 1.0, 93, tie=False,
-                            bp_scale=1e-25 if kind == 'scaled' else None)
-        _CASES[name] = c
+        _CASES[name] = LumCase(**lum_spec(name))
     return _CASES[name]
 
 
@@ -294,14 +310,19 @@ def dev_job(case):
 
 
 def assert_case(case, out, Bp_dev):
-    """B', s, im of every level and the approximate pick of every pixel against the oracle."""
+    """B', s, im of every level and the approximate pick of every pixel against the oracle.
+    out and Bp_dev (indexed by level) hold device tensors, or host arrays read back from a
+    rank process's file (test_gpu_shards.py)."""
+    import torch
     import image_analogies as ia
+    t = lambda x: x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))  # noqa: E731
+    out = {l: (t(v[0]), t(v[1]), tuple(t(x) for x in v[2])) for l, v in out.items()}
     assert set(out) == set(case.ref)
     for l in sorted(case.ref):
         Bp, s, im = case.ref[l]
         assert np.array_equal(out[l][0].cpu().numpy(), s), l
         assert np.array_equal(out[l][1].cpu().numpy(), im), l
-        assert np.array_equal(Bp_dev[l].cpu().numpy(), Bp), l
+        assert np.array_equal(t(Bp_dev[l]).cpu().numpy(), Bp), l
         rec = ia.debug_record(out[l][0], out[l][1], out[l][2], Bp.shape[:2])
         nn, sa, d = case.app[l]
         assert rec['sa'] == sa, l

@@ -330,6 +330,94 @@ def test_oracle_index_takes_lowest_row_of_a_large_tie(nch):
         assert np.array_equal(i0, i2) and np.array_equal(d0, d2)
 
 
+# ---- the inputs of tests/test_gpu_shards.py tie across the ranks as they claim -----------------
+# (the oracle, numpy and the library's host-only geometry calls; floors of 100 finest-level
+# queries, as the one-GPU tie tests use: B's flat half is 384 of 768 pixels)
+
+def _rank_ties(name, world):
+    """Per rank: the tied segments per finest-level query of the rank's shard (shard_ties)."""
+    import test_gpu_shards as sh
+    return [sh.shard_ties(name, r, world)[0] for r in range(world)]
+
+
+@pytest.mark.parametrize('name,world', [('tie2@small', 2), ('tie2@small', 3), ('over@shards', 2),
+                                        ('linear@image', 2)])
+def test_shard_inputs_tie_across_ranks_with_the_winner_on_rank_0(name, world):
+    """At least 100 queries whose nearest row has bit-identical copies in two or more ranks'
+    row ranges, the oracle's winner (the lowest row) in rank 0's."""
+    import test_gpu_shards as sh
+    case = sh.shard_case(name)
+    held = np.array([t > 0 for t in _rank_ties(name, world)])
+    across = held.sum(axis=0) >= 2
+    end0 = sum(sh.shard_rows(len(case.rows), 0, world))
+    print('%s world %d: %d queries tied across ranks, %d of them won on rank 0'
+          % (name, world, across.sum(), (case.nn[across] < end0).sum()))
+    assert across.sum() >= 100 and (case.nn[across] < end0).all()
+    if name == 'over@shards':   # each rank's candidate list overflows
+        for t in _rank_ties(name, world):
+            assert (t > 1024).sum() >= 100, (t > 1024).sum()
+
+
+def test_shard_input_tie_late_wins_on_rank_1_with_nothing_on_rank_0():
+    """tie_late@small over 3 ranks: at least 100 queries whose tied rows lie on ranks 1 and 2
+    and nowhere in rank 0's range; the winner in rank 1's; rank 2's rows are all one row."""
+    import test_gpu_shards as sh
+    case = sh.shard_case('tie_late@small')
+    t0, t1, t2 = _rank_ties('tie_late@small', 3)
+    late = (t0 == 0) & (t1 > 0) & (t2 > 0)
+    N = len(case.rows)
+    r1, n1 = sh.shard_rows(N, 1, 3)
+    r2, n2 = sh.shard_rows(N, 2, 3)
+    print('tie_late@small: %d late queries' % late.sum())
+    assert late.sum() >= 100
+    assert ((case.nn[late] >= r1) & (case.nn[late] < r1 + n1)).all()
+    assert (case.rows[r2:r2 + n2] == case.rows[r2]).all()
+
+
+@pytest.mark.parametrize('name', ['straddle@strip', 'over@shards'])
+def test_shard_inputs_middle_rank_straddles_the_image_boundary(name):
+    """Over 3 ranks the middle rank's range contains the image boundary Ah Aw, its shard is in
+    strip order, and at least 100 queries tie over two or more of its segments on each side of
+    the boundary; over@shards stays at or below 1024 tied segments on every rank."""
+    import test_gpu_shards as sh
+    case = sh.shard_case(name)
+    Ah, Aw = case.pyr[0][case.L - 1].shape
+    N = len(case.rows)
+    row0, nrows = sh.shard_rows(N, 1, 3)
+    assert N == 2 * Ah * Aw and row0 < Ah * Aw < row0 + nrows
+    import ctypes
+    import _ia
+    m = (ctypes.c_int * 3)()
+    _ia.check(_ia.lib().ia_diag_stage_map(row0, nrows, Aw, Ah, m), 'ia_diag_stage_map')
+    assert m[0] == Aw
+    lo = sh.shard_ties(name, 1, 3, keep=lambda g: g < Ah * Aw)
+    hi = sh.shard_ties(name, 1, 3, keep=lambda g: g >= Ah * Aw)
+    assert np.array_equal(lo + hi, sh.shard_ties(name, 1, 3)[0])
+    both = (lo >= 2) & (hi >= 2)
+    print('%s: %d queries tied over >= 2 segments on each side (most %d + %d)' % (name, both.sum(), lo.max(), hi.max()))
+    assert both.sum() >= 100
+    if name == 'over@shards':
+        assert max(t.max() for t in _rank_ties(name, 3)) <= 1024
+
+
+def test_shard_input_padded_ties_with_each_shards_last_row():
+    """padded@shards over 2 ranks: each shard's rows do not fill its chunks, and at least 100
+    queries' nearest row is bit-identical to the shard's last real row, which its padding
+    repeats."""
+    import _ia
+    import test_gpu_shards as sh
+    case = sh.shard_case('padded@shards')
+    N = len(case.rows)
+    for r in range(2):
+        row0, nrows = sh.shard_rows(N, r, 2)
+        assert _ia.lib().ia_db_rows_padded(nrows) > nrows
+        want = int((case.rows[case.nn] == case.rows[row0 + nrows - 1]).all(axis=1).sum())
+        ties, nseg = sh.shard_ties('padded@shards', r, 2)
+        print('padded@shards rank %d: %d queries tied with the last row, over at most %d of %d segments'
+              % (r, want, ties.max(), nseg))
+        assert want >= 100 and ties.max() <= 1024
+
+
 # ---- the inputs of tests/test_gpu_bounds.py have teeth (numpy and the oracle only) -------------
 
 @pytest.mark.parametrize('n', [55, 165])
