@@ -203,6 +203,8 @@ _SIGS = {
     'ia_diag_set_xsplit_min_rows': (ctypes.c_long, [ctypes.c_long]),
     'ia_diag_xsplit_grid': (ctypes.c_int, [ctypes.c_int, ctypes.c_long, ctypes.c_int]),
     'ia_diag_xsplit_counts': (ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
+    'ia_diag_level_plan': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_int)]),
     'ia_diag_wave_rows': (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]),
     'ia_diag_pipe_schedule': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3 + [ctypes.c_int] * 3 +
                               [ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
@@ -265,6 +267,19 @@ def xwave(on=-1):
     the next wave's query rows, in its strip form k_xstrip on strip-order image-form levels;
     1: k_xwave everywhere; 0: the separate kernels); returns the previous value."""
     return lib().ia_diag_set_xwave(int(on))
+
+
+PLAN_KEYS = ('xw', 'form', 'r16', 'rk', 'split', 'peer', 'fused', 'tail', 'nseg', 'seg_rows', 'strips')
+XW_ROWS, XW_IMG, XW_STRIP = 0, 1, 2
+TAIL_FUSED, TAIL_PEER, TAIL_LSH, TAIL_GATHER, TAIL_REC = range(5)
+
+
+def level_plan(args, K=1):
+    """What a level's IaSynthArgs and this process's knobs select (ia_diag_level_plan): a dict of
+    PLAN_KEYS.  Touches no device when args.comm is NULL."""
+    out = (ctypes.c_int * len(PLAN_KEYS))()
+    check(lib().ia_diag_level_plan(ctypes.byref(args), int(K), out), 'ia_diag_level_plan')
+    return dict(zip(PLAN_KEYS, out))
 
 
 def db_image_enabled():

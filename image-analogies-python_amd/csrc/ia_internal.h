@@ -166,6 +166,19 @@ static inline StageMap db_stage_map(long row0, long nrows, int W, int Himg) {
     return m;
 }
 
+// ---- the matcher's view of a level's DB: its form (the image form wherever dbi is given), stage
+// order and segments.  db_view alone derives it from a level's arguments, and refuses a missing
+// DB or an image form on a level it does not apply to (the DB builders lay the rows out)
+struct DbView {
+    const void *db;      // split-f16 rows (may be null with the image form)
+    bool im;             // the image form: img holds its sections
+    ImgDb img;
+    StageMap sm;         // sm.W > 0: strip order
+    long row0, nrows, nseg;
+    int seg_rows;
+};
+int db_view(const DbSrc &src, long row0, long nrows, const void *db, const void *dbi, DbView *v);
+
 struct Best {            // exact winner of a (query, shard): fp64 distance + global row
     double d;
     long long idx;
@@ -295,13 +308,13 @@ struct XArgs {
                                   // the R16 layout, q64 slot 55 = |kappa_skip|^2, amax[1] = A_skip
     gptr<const unsigned char> askc;  // R16 level: per-segment skip codes (r16_askc, ia_rot16.h)
     // a level with compact waves (ia_rot16.h RK_*): rk != 0, the next query rows carry the compact
-    // operands too; a compact wave (k_xstrip<false, true, true>; nullable otherwise): the
+    // operands too; a compact wave (XwVariant::cmp; nullable otherwise): the
     // segments' rest-norm codes and Rmax, and this wave's q16 rows (|kappa_rest|^2)
     int rk;
     gptr<const unsigned char> restc;
     gptr<const float> rmax;
     gptr<const _Float16> q16;
-    // split candidates (k_xstrip<false, true, CMP, true>; nullable otherwise): the helpers' records,
+    // split candidates (XwVariant::split; nullable otherwise): the helpers' records,
     // 8 tagged granules per image row; the launch then has two workgroups per pixel
     gptr<unsigned long long> xbox;
 };
@@ -313,7 +326,37 @@ constexpr int XW_TRACE_N = 17, XW_TRACE_PX = 512, XW_TRACE_T = 4096;
 // (strip-order image form: k_xstrip, fp64 windows; xstrip_applies)
 constexpr int XW_ROWS = 0, XW_IMG = 1, XW_STRIP = 2;
 bool xstrip_applies(const DbSrc &src);
-int launch_xwave(const XArgs &a, int nblocks, int form, hipStream_t st, int njobs = 1);
+// one built instance of the fused kernel: k_xwave by form and batch (it takes the R16 bound at
+// run time, XArgs::rot) or k_xstrip (XW_STRIP) by batch, rot, cmp and split
+struct XwVariant {
+    int form;
+    bool batch, rot, cmp, split;
+};
+const void *xwave_kernel(XwVariant v);   // null (error set): no such instance is built
+int xwave_attributes(XwVariant v, hipFuncAttributes *at);
+// nblocks workgroups (x njobs) of variant v; a's operands must be the ones v reads
+int launch_xwave(const XArgs &a, int nblocks, XwVariant v, hipStream_t st, int njobs = 1);
+
+// ---- what a level's arguments and the process's knobs select: everything that is
+// the same for all of a level's waves, decided once per level by level_plan (ia_synth.hip).  The
+// knobs are read there and nowhere later: a level keeps the form it started with.
+// the per-pixel tail without the fused kernel: the exact stage's own (one GPU), k_peer_finish,
+// k_lsh_tail, k_finish_gather (RCCL), k_finish (RCCL with IA_SHARD_TAIL=1; the shard simulation)
+enum TailKind { TAIL_FUSED, TAIL_PEER, TAIL_LSH, TAIL_GATHER, TAIL_REC, TAIL_SIM };
+struct LevelPlan {
+    int nranks;        // of the comm (1 without)
+    bool peer, fused;  // the device-side exchange; tail == TAIL_FUSED
+    bool xw, r16;      // one fused launch per wave after the screen; the R16 screen and bound
+    int form;          // XW_ROWS / XW_IMG / XW_STRIP, -1 without xw
+    bool rk, split;    // the level has compact waves (wave_compact); two workgroups per pixel
+    int tail;          // TailKind
+    DbView v;          // (zeroed on LSH and simulated levels: their DBs are not the level's)
+    XwVariant variant(int K, bool cmp) const { return XwVariant{form, K > 1, r16, cmp, split}; }
+};
+int level_plan(const IaSynthArgs &a, int K, bool sim, LevelPlan *p);
+// a strip-order level that k_xstrip serves, of at least the compact form's rows: what rk and
+// ia_db_rotk_applies both start from
+bool compact_level(const DbSrc &src, const StageMap &sm, long nrows);
 
 // matcher statistics (profiling only): per-query counters are spread over STATS_SLOTS
 // cache lines so that the atomics of a wave's M queries do not serialise on one address;
@@ -347,10 +390,6 @@ int launch_query_wave(const ImgPair &B, const ImgPair &Bp, int t, int y_lo, int 
 int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Float16 *q16, int M,
                      float *segmin, hipStream_t st, const XJob *jobs = nullptr, int njobs = 1, int parity = 0,
                      bool compact = false);
-// the compact form's row threshold (ia_diag_set_compact_min_rows; LONG_MAX: off)
-long compact_min_rows();
-// the split tail's row threshold (ia_diag_set_xsplit_min_rows; LONG_MAX: off)
-long xsplit_min_rows();
 // amax = max(amax, the split scale's bound of a level's four value ranges) (ia_features.hip);
 // part: DBB_BLOCKS x 8 doubles of scratch
 int launch_db_amax(const IaSrcLevel *src, const DbSrc &d, const double *center, float *amax,

@@ -451,6 +451,21 @@ size_t match_scratch_bytes(int qrows, long nrows) {
            align_up(n * sizeof(Best), 256) + align_up((size_t)qrows * sizeof(QSel), 256);
 }
 
+int db_view(const DbSrc &src, long row0, long nrows, const void *db, const void *dbi, DbView *v) {
+    *v = DbView{};
+    IA_ARG(db || dbi, "db_view: no DB (row form or image form)");
+    IA_ARG(!dbi || img_db_layout(src.A.h, src.A.w, src.A.hs, src.A.ws, 1, row0, nrows, dbi, v->img, nullptr),
+           "db_view: an image-form DB for a level it does not apply to");
+    v->db = db;
+    v->im = dbi != nullptr;
+    v->sm = db_stage_map(row0, nrows, src.A.w, src.A.h);
+    v->row0 = row0;
+    v->nrows = nrows;
+    v->nseg = db_nsegs(nrows);
+    v->seg_rows = db_seg_rows(nrows);
+    return IA_OK;
+}
+
 int launch_match(const DbSrc &src, long row0, long nrows, const void *dbv, const void *dbi,
                  const float *qp, const _Float16 *q16, int M, const double *q64, const double *nq,
                  const float *amax, void *scratch, Best *best, unsigned long long *stats,
@@ -458,24 +473,20 @@ int launch_match(const DbSrc &src, long row0, long nrows, const void *dbv, const
     int rc;
     IA_ARG(q16, "launch_match: no split-f16 query rows");
     const half8 *db = reinterpret_cast<const half8 *>(dbv);
-    ImgDb img{};
-    IA_ARG(!dbi || img_db_layout(src.A.h, src.A.w, src.A.hs, src.A.ws, 1, row0, nrows, dbi, img, nullptr),
-           "launch_match: an image-form DB for a level it does not apply to");
-    IA_ARG(db || dbi, "launch_match: no DB (row form or image form)");
+    DbView v;
+    if ((rc = db_view(src, row0, nrows, dbv, dbi, &v))) return rc;
+    const ImgDb &img = v.img;
+    const StageMap &sm = v.sm;
+    const bool im = v.im;   // (the exact stage re-screens from the image form whenever there is one)
     const SegWs ws = seg_ws(scratch, M, nrows);
     if (ev0) IA_HIP(hipEventRecord(ev0, st));
-    const StageMap sm = db_stage_map(row0, nrows, src.A.w, src.A.h);
     // (the unfused matcher also serves sharded levels whose tails wait for other ranks: the
     // 4-wave screen here, never the one-block-per-CU producer / consumer form)
-    if ((rc = launch_screen16(db, dbi ? &img : nullptr, nrows, sm, q16, M, ws.segmin, st, nullptr, 1, 0,
-                              true)))
+    if ((rc = launch_screen16(db, im ? &img : nullptr, nrows, sm, q16, M, ws.segmin, st, nullptr, 1, 0, true)))
         return rc;
     if (ev1) IA_HIP(hipEventRecord(ev1, st));
     const FinishArgs fa = fin ? *fin : FinishArgs{};
     const int rm = rescore_mode();
-    // the exact stage re-screens from the image form whenever there is one (the row form
-    // need not exist then)
-    const bool im = dbi != nullptr;
     // default: k_rescore (one workgroup per query, with or without the fused tail; a
     // sharded rank's 0.5 M-row shard: 13.9 vs 19.9 us per wave, profiles/r01_shard_sim_g8.txt),
     // except on row-form levels above 2^20 rows, where its per-query serialisation costs
@@ -686,28 +697,34 @@ int ia_diag_screen16(const void *db, long nrows, const void *q16, int M, float *
 
 int ia_diag_stage_map(long row0, long nrows, int W, int Himg, int *out) {
     IA_ARG(out && nrows > 0 && row0 >= 0, "ia_diag_stage_map: bad args");
-    const StageMap m = db_stage_map(row0, nrows, W, Himg);
-    out[0] = m.W;
-    out[1] = m.nstrip;
-    out[2] = m.sc;
+    DbSrc geo{};   // (a row-form DB of that geometry; `out` stands in for its rows, never read)
+    geo.A.w = W; geo.A.h = Himg;
+    DbView v;
+    const int rc = db_view(geo, row0, nrows, out, nullptr, &v);
+    if (rc) return rc;
+    out[0] = v.sm.W; out[1] = v.sm.nstrip; out[2] = v.sm.sc;
     return IA_OK;
+}
+
+// one split-f16 screen over the view of (db, dbi)
+static int diag_screen16(const char *who, const IaSrcLevel *src, long row0, long nrows, const void *db,
+                         const void *dbi, const void *q16, int M, float *segmin, void *stream) {
+    IA_ARG(src && (db || dbi) && q16 && segmin && M > 0 && nrows > 0, std::string(who) + ": bad args");
+    DbView v;
+    const int rc = db_view(make_dbsrc(*src), row0, nrows, db, dbi, &v);
+    if (rc) return rc;
+    return launch_screen16(v.db, v.im ? &v.img : nullptr, nrows, v.sm, reinterpret_cast<const _Float16 *>(q16), M,
+                           segmin, S(stream));
 }
 
 int ia_diag_screen16_rows(const IaSrcLevel *src, long row0, long nrows, const void *db,
                           const void *q16, int M, float *segmin, void *stream) {
-    IA_ARG(src && db && q16 && segmin && M > 0 && nrows > 0, "ia_diag_screen16_rows: bad args");
-    return launch_screen16(db, nullptr, nrows, db_stage_map(row0, nrows, src->Aw, src->Ah),
-                           reinterpret_cast<const _Float16 *>(q16), M, segmin, S(stream));
+    return diag_screen16("ia_diag_screen16_rows", src, row0, nrows, db, nullptr, q16, M, segmin, stream);
 }
 
 int ia_diag_screen16_image(const IaSrcLevel *src, long row0, long nrows, const void *dbi,
                            const void *q16, int M, float *segmin, void *stream) {
-    IA_ARG(src && dbi && q16 && segmin && M > 0 && nrows > 0, "ia_diag_screen16_image: bad args");
-    ImgDb img;
-    IA_ARG(img_db_layout(src->Ah, src->Aw, src->A_hs, src->A_ws, src->nAp, row0, nrows, dbi, img, nullptr),
-           "ia_diag_screen16_image: the image form does not apply to this level");
-    return launch_screen16(nullptr, &img, nrows, db_stage_map(row0, nrows, src->Aw, src->Ah),
-                           reinterpret_cast<const _Float16 *>(q16), M, segmin, S(stream));
+    return diag_screen16("ia_diag_screen16_image", src, row0, nrows, nullptr, dbi, q16, M, segmin, stream);
 }
 
 }  // extern "C"

@@ -171,7 +171,7 @@ __device__ __forceinline__ void r16_thresholds_rows(float emin, float amax0, flo
 // instead of two; A and |q'| bound |rho_C| and |kappa_C|; A_skip,j and |kappa_skip| of components
 // P..54 bound those of P..C-1, so the 64-slot form's codes serve); the rotation's 30u A|q'| now
 // pays for D against |rho - kappa|^2, whose other parts are 15u A^2 (85.4 + 15 <= RK_EPS_A2) and
-// 30u |q'|^2.  The exact stage (k_xstrip<.., true, true>) rescores one segment exactly first
+// 30u |q'|^2.  The exact stage (k_xstrip's compact form) rescores one segment exactly first
 // (any: it takes the least L_j), U = its fp64 minimum, and then every segment with L_j <= U:
 // the oracle's winner r_o (segment o) has L_o <= D(r_o) <= U.
 // Layouts.  DB: per 32-row tile 4 groups x 32 rows x half8 (group g = slots 8g .. 8g + 7: lane

@@ -1054,12 +1054,8 @@ int ia_db_rot_applies(const IaSrcLevel *src, long row0, long nrows) {
 int ia_screen_resources(int which, int *lds, int *vgprs) {
     IA_ARG(lds && vgprs && (which == 0 || which == 1), "ia_screen_resources: bad args");
     hipFuncAttributes at{};
-    if (which == 0) {
-        IA_HIP(hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_screen16r<11>)));
-    } else {
-        int rc = screen16i_attributes(&at);
-        if (rc) return rc;
-    }
+    const int rc = which == 0 ? screen_resources_r16(&at) : screen16i_attributes(&at);
+    if (rc) return rc;
     *lds = (int)at.sharedSizeBytes;
     *vgprs = at.numRegs;
     return IA_OK;
@@ -1133,10 +1129,10 @@ size_t ia_db_rotk_bytes(long nrows) { return nrows > 0 && RK_BUILT ? rk_bytes(nr
 
 int ia_db_rotk_applies(const IaSrcLevel *src, long row0, long nrows) {
     // single-shard strip-order levels of the fused strip kernel at or above the row threshold
-    if (!RK_BUILT || !ia_db_rot_applies(src, row0, nrows) || nrows < compact_min_rows()) return 0;
+    if (!RK_BUILT || !ia_db_rot_applies(src, row0, nrows)) return 0;
     if (row0 != 0 || nrows != (long)src->nAp * src->Ah * src->Aw) return 0;
-    const DbSrc d = make_dbsrc(*src);
-    return db_stage_map(row0, nrows, src->Aw, src->Ah).W > 0 && xstrip_applies(d) && db_seg_rows(nrows) >= 128 ? 1 : 0;
+    return compact_level(make_dbsrc(*src), db_stage_map(row0, nrows, src->Aw, src->Ah), nrows) &&
+                   db_seg_rows(nrows) >= 128 ? 1 : 0;
 }
 
 int ia_db_build_rotk(const IaSrcLevel *src, long row0, long nrows, const double *center, const float *rot,
@@ -1169,34 +1165,38 @@ int ia_db_build_rotk(const IaSrcLevel *src, long row0, long nrows, const double 
     return IA_OK;
 }
 
-/* diagnostics: one R16 screen of M fp64 query rows (IA_DP each) over a rotated DB ->
- * segmin[M][db_nsegs(nrows)] (screen units), nq[M], nsk[M]; q16: qrows_alloc(M) rows of
- * Q16_ROW half8, zeroed by the caller */
+/* diagnostics: one R16 screen of M fp64 query rows (IA_DP each) over a rotated DB (compact: over
+ * dbk, ia_db_build_rotk) -> segmin[M][db_nsegs(nrows)] (screen units), nq[M], nsk[M]; q16:
+ * qrows_alloc(M) rows of Q16_ROW half8, zeroed by the caller */
+static int diag_screen16r(const char *who, bool compact, const IaSrcLevel *src, long row0, long nrows,
+                          const void *dbr, const float *rot, const float *amax, const double *center,
+                          const double *q64, int M, void *q16, double *nq, double *nsk, float *segmin,
+                          void *stream) {
+    IA_ARG(src && dbr && rot && amax && center && q64 && q16 && nq && nsk && segmin && M > 0,
+           std::string(who) + ": bad args");
+    hipStream_t st = S(stream);
+    int rc = launch_query_rows_r16(q64, M, center, rot, amax, nq, nsk, reinterpret_cast<_Float16 *>(q16), st, compact);
+    if (rc) return rc;
+    DbView v;   // (the rotated rows follow the level's stage order)
+    if ((rc = db_view(make_dbsrc(*src), row0, nrows, dbr, nullptr, &v))) return rc;
+    return launch_screen16r(dbr, nrows, v.sm, reinterpret_cast<const _Float16 *>(q16), M, segmin, st, nullptr, 1, 0,
+                            compact);
+}
+
 int ia_diag_screen16r(const IaSrcLevel *src, long row0, long nrows, const void *dbr, const float *rot,
                       const float *amax, const double *center, const double *q64, int M, void *q16,
                       double *nq, double *nsk, float *segmin, void *stream) {
-    IA_ARG(src && dbr && rot && amax && center && q64 && q16 && nq && nsk && segmin && M > 0,
-           "ia_diag_screen16r: bad args");
-    hipStream_t st = S(stream);
-    int rc = launch_query_rows_r16(q64, M, center, rot, amax, nq, nsk, reinterpret_cast<_Float16 *>(q16), st);
-    if (rc) return rc;
-    const StageMap sm = db_stage_map(row0, nrows, src->Aw, src->Ah);
-    return launch_screen16r(dbr, nrows, sm, reinterpret_cast<const _Float16 *>(q16), M, segmin, st, nullptr, 1, 0);
+    return diag_screen16r("ia_diag_screen16r", false, src, row0, nrows, dbr, rot, amax, center, q64, M, q16, nq,
+                          nsk, segmin, stream);
 }
 
-/* the same with the compact screen over dbk (ia_db_build_rotk): segmin holds lower bounds
- * only; |kappa_rest|^2 of query m is the double at byte 192 of its q16 row */
+/* the same with the compact screen over dbk: segmin holds lower bounds only; |kappa_rest|^2 of
+ * query m is the double at byte 192 of its q16 row */
 int ia_diag_screen16k(const IaSrcLevel *src, long row0, long nrows, const void *dbk, const float *rot,
                       const float *amax, const double *center, const double *q64, int M, void *q16,
                       double *nq, double *nsk, float *segmin, void *stream) {
-    IA_ARG(src && dbk && rot && amax && center && q64 && q16 && nq && nsk && segmin && M > 0,
-           "ia_diag_screen16k: bad args");
-    hipStream_t st = S(stream);
-    int rc = launch_query_rows_r16(q64, M, center, rot, amax, nq, nsk, reinterpret_cast<_Float16 *>(q16), st, true);
-    if (rc) return rc;
-    const StageMap sm = db_stage_map(row0, nrows, src->Aw, src->Ah);
-    return launch_screen16r(dbk, nrows, sm, reinterpret_cast<const _Float16 *>(q16), M, segmin, st, nullptr, 1, 0,
-                            true);
+    return diag_screen16r("ia_diag_screen16k", true, src, row0, nrows, dbk, rot, amax, center, q64, M, q16, nq,
+                          nsk, segmin, stream);
 }
 
 }  // extern "C"

@@ -313,7 +313,7 @@ static int graph_mode() { return g_graph_mode.load(std::memory_order_relaxed); }
 // the compact screen's level threshold (rows; DESIGN.md §4d: c4's finest level pays, measured);
 // LONG_MAX: off (ia_diag_set_compact_min_rows)
 static std::atomic<long> g_compact_min_rows{1L << 22};
-long compact_min_rows() { return g_compact_min_rows.load(std::memory_order_relaxed); }
+static long compact_min_rows() { return g_compact_min_rows.load(std::memory_order_relaxed); }
 // compact waves enqueued by this process (ia_diag_compact_waves: the tests' proof that the form ran)
 static std::atomic<long> g_compact_waves{0};
 // the split tail's level threshold (rows; DESIGN.md §6b "split": a pixel's candidate segments over
@@ -325,14 +325,13 @@ static long xsplit_initial() {
     return v > 0 ? v : LONG_MAX;
 }
 static std::atomic<long> g_xsplit_min_rows{xsplit_initial()};
-long xsplit_min_rows() { return g_xsplit_min_rows.load(std::memory_order_relaxed); }
+static long xsplit_min_rows() { return g_xsplit_min_rows.load(std::memory_order_relaxed); }
 // workgroups of the fused kernel's launch for R pixel rows: two per pixel where the split applies
 // (eligible: one unsharded job's strip-form R16 level), else one
 static int xsplit_grid(bool eligible, long nrows, int R) {
     return eligible && nrows >= xsplit_min_rows() && db_nsegs(nrows) <= (1L << 20) ? 2 * R : R;
 }
 
-int xwave_attributes(int form, bool rot, hipFuncAttributes *at);
 int screen16_attributes(bool img, hipFuncAttributes *at);
 int screen_resources_r16(hipFuncAttributes *at);
 int comm_allgather(void *comm, const void *send, void *recv, size_t bytes, hipStream_t st);
@@ -370,6 +369,40 @@ static unsigned long long *xw_trace(int tag) {
     return g_xw_trace;
 }
 
+bool compact_level(const DbSrc &src, const StageMap &sm, long nrows) {
+    return sm.W > 0 && xstrip_applies(src) && nrows >= compact_min_rows();
+}
+
+// The one place a level's launch forms are decided (ia_internal.h LevelPlan).
+// K: the jobs sharing the level's launches; sim: the in-process shard simulation.
+int level_plan(const IaSynthArgs &a, int K, bool sim, LevelPlan *p) {
+    LevelPlan &l = *p;
+    l = LevelPlan{};
+    l.form = -1;
+    l.nranks = comm_nranks(a.comm);
+    // the device-side exchange: the exact stage (or the fused kernel) publishes, no RCCL call
+    l.peer = a.comm && comm_peer_mcap(a.comm) > 0;
+    l.tail = sim ? TAIL_SIM : a.lsh ? TAIL_LSH : l.peer ? TAIL_PEER
+           : a.comm ? (shard_tail() ? TAIL_REC : TAIL_GATHER) : TAIL_FUSED;
+    l.fused = l.tail == TAIL_FUSED;
+    // one launch per wave after the screen wherever the exact matcher runs on one GPU or over
+    // the device-side exchange (not the LSH matcher, RCCL, the simulation or a forced work list)
+    const int xwave = xwave_on();
+    l.xw = xwave && !a.lsh && !sim && (!a.comm || l.peer) && exact_stage_mode() != 1;
+    l.r16 = l.xw && a.dbr && a.rot;   // (either form of the fused kernel takes the R16 bound)
+    if (a.lsh || sim) return IA_OK;
+    const DbSrc src = make_dbsrc(a.src);
+    const int rc = db_view(src, a.row0, a.nrows, a.db, a.dbi, &l.v);
+    if (rc || !l.xw) return rc;
+    l.form = !l.v.im ? XW_ROWS : (xwave == 2 && l.v.sm.W > 0 && xstrip_applies(src)) ? XW_STRIP : XW_IMG;
+    // compact waves (ia_rot16.h RK_*) and split candidates: one unsharded job's strip-form R16
+    // level, above each one's row threshold
+    const bool one = l.r16 && K == 1 && !a.comm && l.form == XW_STRIP;
+    l.rk = one && a.dbk && compact_level(src, l.v.sm, a.nrows);
+    l.split = xsplit_grid(one, a.nrows, 1) == 2;
+    return IA_OK;
+}
+
 static int check_args(const IaSynthArgs *a) {
     IA_ARG(a && (a->db || a->dbi || a->lsh) && a->center && a->amax && a->B_sm && a->B_lg && a->Bp_sm && a->Bp_lg &&
                a->weights && a->s && a->im && a->workspace,
@@ -397,14 +430,13 @@ struct LevelRun {
     DbSrc src{};
     ImgPair B{}, Bp{};
     int H = 0, W = 0, nw = 0, nranks = 1;
-    bool prof = false, timed = false, fused = false, peer = false, xw = false;
+    bool prof = false, timed = false;
+    LevelPlan plan{};        // the level's launch forms, decided once (init)
+    XArgs xa{};              // the fused kernel's arguments that no wave changes (plan.xw)
     // a batch of K identical-shape jobs (ia_synth_levels_batch): this run is job 0 and owns
     // the launches; part[k - 1] holds job k's state (member runs record no profile)
     int K = 1;
     bool member = false;
-    // R16 (ia_rot16.h): the rotated DB and rotation given, on a strip-order level of the fused
-    // kernel: the rotated screen, rotated query rows and k_xstrip's R16 bound
-    bool r16 = false;
     std::vector<LevelRun> part;
     size_t ev0 = 0;
     unsigned long long *hstats = nullptr;
@@ -412,11 +444,12 @@ struct LevelRun {
     int nscreen = 0;
     std::vector<int> Ms;
 
-    int init(const IaSynthArgs *args, hipStream_t st) {
+    int init(const IaSynthArgs *args, hipStream_t st, int njobs = 1) {
         a = args;
+        K = njobs;
         int rc = check_args(a);
-        if (rc) return rc;
-        nranks = a->comm ? comm_nranks(a->comm) : (sim ? nsim : 1);
+        if (rc || (rc = level_plan(*a, K, sim != nullptr, &plan))) return rc;
+        nranks = sim ? nsim : plan.nranks;
         H = a->H; W = a->W;
         nw = wave_count(H, W);
         long rows_ws = a->nrows;
@@ -433,31 +466,51 @@ struct LevelRun {
         prof = !member && (a->flags & IA_SYNTH_PROF) && prof_active();
         timed = prof;
         if (prof && (rc = prof_reserve(3 * (size_t)nw, &ev0, &hstats))) return rc;
-        // fused tail (one launch + one round trip less per wave): on a single shard the exact
-        // stage's last kernel (k_rescore, or k_gather of the work list) runs the pixel tail;
-        // on a sharded DB it prepares the tail (coherence pick, the winner's weighted
-        // distance) before the exchange
-        fused = !a->comm && !a->lsh && !sim;
-        // sharded level over the device-side exchange: the exact stage's kernel publishes,
-        // k_peer_finish collects and finishes each pixel (no RCCL call)
-        peer = a->comm && comm_peer_mcap(a->comm) > 0;
-        IA_ARG(!peer || comm_peer_mcap(a->comm) >= Mmax,
+        IA_ARG(!plan.peer || comm_peer_mcap(a->comm) >= Mmax,
                "ia_synth_level: the peer exchange's box holds fewer queries than a wave");
-        IA_ARG(!peer || a->N_total < (1L << 32),
+        IA_ARG(!plan.peer || a->N_total < (1L << 32),
                "ia_synth_level: the peer exchange carries 32-bit rows (N_total >= 2^32)");
-        // one launch per wave after the screen (k_xwave) wherever the exact matcher runs
-        // on one GPU or over the device-side exchange (not the LSH matcher, the RCCL
-        // exchange, the in-process shard simulation or a forced work list)
-        xw = xwave_on() && !a->lsh && !sim && (!a->comm || peer) && exact_stage_mode() != 1;
-        // (any form of the fused kernel: k_xstrip on strip-order levels, k_xwave elsewhere)
-        r16 = xw && a->dbr && a->rot;
         IA_HIP(hipMemsetAsync(ws.ctl, 0, 256, st));   // tickets, error word (ia_synth_status)
-        if (xw) {
-            IA_HIP(hipMemsetAsync(ws.qpb, 0, (size_t)qrows_alloc(Mmax) * IA_DP * sizeof(float), st));
-            IA_HIP(hipMemsetAsync(ws.q16b, 0, (size_t)qrows_alloc(Mmax) * Q16_ROW * 16, st));
-            IA_HIP(hipMemsetAsync(ws.dbox, 0, (size_t)H * 2 * sizeof(unsigned long long), st));
-            IA_HIP(hipMemsetAsync(ws.xbox, 0, (size_t)H * 8 * sizeof(unsigned long long), st));
-        }
+        if (!plan.xw) return IA_OK;
+        IA_HIP(hipMemsetAsync(ws.qpb, 0, (size_t)qrows_alloc(Mmax) * IA_DP * sizeof(float), st));
+        IA_HIP(hipMemsetAsync(ws.q16b, 0, (size_t)qrows_alloc(Mmax) * Q16_ROW * 16, st));
+        IA_HIP(hipMemsetAsync(ws.dbox, 0, (size_t)H * 2 * sizeof(unsigned long long), st));
+        IA_HIP(hipMemsetAsync(ws.xbox, 0, (size_t)H * 8 * sizeof(unsigned long long), st));
+        const DbView &v = plan.v;
+        xa.src = src; xa.im = v.img; xa.db = v.db;
+        xa.row0 = v.row0; xa.nrows = v.nrows; xa.nseg = v.nseg; xa.seg_rows = v.seg_rows; xa.smap = v.sm;
+        xa.segmin = match_segmin(ws.scratch);
+        xa.amax = a->amax; xa.center = a->center;
+        xa.B = B; xa.Bp = Bp; xa.H = H;
+        xa.dbox = ws.dbox; xa.tickets = ws.ctl; xa.err = ws.ctl + XW_CTL_ERR;
+        xa.stats = prof ? ws.stats : nullptr;
+        xa.f = finish_args(0, 0, nullptr, nullptr);
+        xa.jobs = K > 1 ? ws.jtab : nullptr;
+        xa.trace = xw_trace(a->tag);
+        xa.rot = plan.r16 ? a->rot : nullptr;
+        xa.askc = plan.r16 ? r16_askc(a->dbr, a->nrows) : nullptr;
+        xa.rk = plan.rk ? 1 : 0;
+        return IA_OK;
+    }
+
+    // wave t's view of the level state the per-pixel tail updates
+    FinishArgs finish_args(int t, int y_lo, ShardRec *shard_out, CohSel *coh_out) const {
+        return FinishArgs{t, y_lo, W, a->N_total, a->weights, a->kappa_factor, a->Bp_lg, a->s,
+                          a->im, a->dbg_px, a->dbg_dist, shard_out, coh_out};
+    }
+
+    // this wave's profiling events (null unless timed): 0 / 1 bracket the screen, 2 follows the
+    // exact stage (the unfused tails are not bracketed)
+    hipEvent_t wave_event(int i) const { return timed ? prof_event(ev0 + 3 * nscreen + i) : nullptr; }
+    // after wave t's exact stage: event 2, the profile's counts and the IA_SYNC_EVERY=n wait (every n
+    // waves: bounds the dispatches in flight, rocprofv3 --pmc runs of the whole bench crash otherwise)
+    int wave_counted(int t, int M, hipStream_t sq) {
+        if (timed) IA_HIP(hipEventRecord(wave_event(2), sq));
+        ++nscreen;
+        pairs += (double)M * (double)a->nrows * K;
+        if (prof) Ms.push_back(M);
+        static const int sync_every = env_int("IA_SYNC_EVERY", 0);
+        if (sync_every > 0 && t % sync_every == sync_every - 1) IA_HIP(hipStreamSynchronize(sq));
         return IA_OK;
     }
 
@@ -466,19 +519,17 @@ struct LevelRun {
         wave_rows(H, W, t, y_lo, M);
         if (M <= 0) return IA_OK;
         int rc;
-        if (sim) return sim_wave(t, y_lo, M, sq);
-        if (xw) return xw_wave(t, y_lo, M, sq);
+        const int tail = plan.tail;
+        if (tail == TAIL_SIM) return sim_wave(t, y_lo, M, sq);
+        if (plan.xw) return xw_wave(t, y_lo, M, sq);
         if ((rc = launch_query_wave(B, Bp, t, y_lo, M, a->center, ws.q64, ws.qp, ws.nq, a->amax,
                                     ws.q16, sq)))
             return rc;
-        hipEvent_t e0 = timed ? prof_event(ev0 + 3 * nscreen) : nullptr;
-        hipEvent_t e1 = timed ? prof_event(ev0 + 3 * nscreen + 1) : nullptr;
-        FinishArgs fa{t, y_lo, W, a->N_total, a->weights, a->kappa_factor, a->Bp_lg, a->s,
-                      a->im, a->dbg_px, a->dbg_dist,
-                      a->comm && !peer && shard_tail() ? ws.rec_local : nullptr,
-                      a->comm && !peer && shard_tail() ? ws.coh : nullptr};
-        if (peer) fa.px = comm_peer_wave(a->comm);
-        if (a->lsh) {   // approximate matcher: the events bracket the LSH query kernel
+        hipEvent_t e0 = wave_event(0), e1 = wave_event(1);
+        FinishArgs fa = finish_args(t, y_lo, tail == TAIL_REC ? ws.rec_local : nullptr,
+                                    tail == TAIL_REC ? ws.coh : nullptr);
+        if (tail == TAIL_PEER) fa.px = comm_peer_wave(a->comm);
+        if (tail == TAIL_LSH) {   // approximate matcher: the events bracket the LSH query kernel
             if (e0) IA_HIP(hipEventRecord(e0, sq));
             if ((rc = launch_lsh_match(a->lsh, src, a->row0, a->nrows, M, ws.q64, a->center,
                                        ws.best_local, prof ? ws.stats : nullptr, sq)))
@@ -487,44 +538,35 @@ struct LevelRun {
         } else if ((rc = launch_match(src, a->row0, a->nrows, a->db, a->dbi, ws.qp, ws.q16, M, ws.q64, ws.nq,
                                       a->amax, ws.scratch, ws.best_local,
                                       prof ? ws.stats : nullptr, sq, e0, e1,
-                                      (fused || peer || (a->comm && shard_tail())) ? &fa : nullptr))) {
+                                      tail == TAIL_GATHER ? nullptr : &fa))) {
             return rc;
         }
-        ++nscreen;
-        pairs += (double)M * (double)a->nrows;
-        if (prof) Ms.push_back(M);
-        // diagnostic (IA_SYNC_EVERY=n): wait for the stream every n waves, bounding the
-        // dispatches in flight (rocprofv3 --pmc runs of the whole bench crash otherwise)
-        static const int sync_every = env_int("IA_SYNC_EVERY", 0);
-        if (sync_every > 0 && t % sync_every == sync_every - 1) IA_HIP(hipStreamSynchronize(sq));
-        // e2 of this wave: right after the exact stage (the unfused tails are not bracketed)
-        if (timed) IA_HIP(hipEventRecord(prof_event(ev0 + 3 * (nscreen - 1) + 2), sq));
-        if (fused) return IA_OK;   // the exact stage already ran the per-pixel tail
-        if (peer) {                // collect the ranks' winners, finish the pixel
+        if ((rc = wave_counted(t, M, sq))) return rc;
+        switch (tail) {
+        case TAIL_FUSED:    // the exact stage already ran the per-pixel tail
+            return IA_OK;
+        case TAIL_PEER:     // collect the ranks' winners, finish the pixel
             k_peer_finish<<<M, 128, 0, sq>>>(src, ws.best_local, fa, ws.q64);
-            IA_LAUNCH_CHECK("k_peer_finish");
-            return IA_OK;
-        }
-        if (a->lsh) {   // one shard, LSH winners: the tail in k_lsh_finish form
+            break;
+        case TAIL_LSH:      // one shard, LSH winners
             k_lsh_tail<<<M, 128, 0, sq>>>(src, ws.best_local, M, fa, ws.q64);
-            IA_LAUNCH_CHECK("k_lsh_tail");
-            return IA_OK;
-        }
-        // sharded DB: the exact stage left this rank's records and coherence picks; the
-        // exchange (also with one rank: the same RCCL path, exercised by the tests), then
-        // the finish
-        if (!shard_tail()) {
+            break;
+        // sharded DB over RCCL (also with one rank: the same path, exercised by the tests): the
+        // exchange of the ranks' winners, or of the records and coherence picks the exact stage
+        // left, then the finish
+        case TAIL_GATHER: {
             Best *all = reinterpret_cast<Best *>(ws.rec_all);
             if ((rc = comm_allgather(a->comm, ws.best_local, all, (size_t)M * sizeof(Best), sq)))
                 return rc;
             k_finish_gather<<<M, 128, 0, sq>>>(src, all, nranks, M, fa, ws.q64);
-            IA_LAUNCH_CHECK("k_finish_gather");
-            return IA_OK;
+            break;
         }
-        if ((rc = comm_allgather(a->comm, ws.rec_local, ws.rec_all, (size_t)M * sizeof(ShardRec), sq)))
-            return rc;
-        k_finish<<<M, 64, 0, sq>>>(src, ws.rec_all, ws.coh, nranks, M, fa);
-        IA_LAUNCH_CHECK("k_finish");
+        default:
+            if ((rc = comm_allgather(a->comm, ws.rec_local, ws.rec_all, (size_t)M * sizeof(ShardRec), sq)))
+                return rc;
+            k_finish<<<M, 64, 0, sq>>>(src, ws.rec_all, ws.coh, nranks, M, fa);
+        }
+        IA_LAUNCH_CHECK("the unfused tail");
         return IA_OK;
     }
 
@@ -532,9 +574,7 @@ struct LevelRun {
     XJob job_entry() const {
         XJob J{};
         J.A_sm = a->src.A_sm; J.A_lg = a->src.A_lg; J.Ap_sm = a->src.Ap_sm; J.Ap_lg = a->src.Ap_lg;
-        ImgDb img{};
-        if (a->dbi)
-            img_db_layout(src.A.h, src.A.w, src.A.hs, src.A.ws, 1, a->row0, a->nrows, a->dbi, img, nullptr);
+        const ImgDb &img = plan.v.img;
         J.fa = img.fa; J.ca = img.ca; J.norm = img.norm; J.ap = img.ap;
         J.db = a->db;
         J.segmin = match_segmin(ws.scratch);
@@ -542,32 +582,28 @@ struct LevelRun {
         J.qp[0] = ws.qp; J.qp[1] = ws.qpb;
         J.nq[0] = ws.nq; J.nq[1] = ws.nqb;
         J.q16[0] = ws.q16; J.q16[1] = ws.q16b;
-        J.amax = a->amax;
-        J.center = a->center;
+        J.amax = a->amax; J.center = a->center;
         J.B_sm = a->B_sm; J.B_lg = a->B_lg; J.Bp_sm = a->Bp_sm; J.Bp_lg = a->Bp_lg;
-        J.weights = a->weights;
-        J.kappa_factor = a->kappa_factor;
+        J.weights = a->weights; J.kappa_factor = a->kappa_factor;
         J.s = a->s; J.im = a->im; J.dbg_px = a->dbg_px; J.dbg_dist = a->dbg_dist;
-        J.dbox = ws.dbox;
-        J.ctl = ws.ctl;
-        J.dbr = r16 ? a->dbr : nullptr;
-        J.askc = r16 ? r16_askc(a->dbr, a->nrows) : nullptr;
-        J.rot = r16 ? a->rot : nullptr;
+        J.dbox = ws.dbox; J.ctl = ws.ctl;
+        J.dbr = plan.r16 ? a->dbr : nullptr;
+        J.askc = plan.r16 ? r16_askc(a->dbr, a->nrows) : nullptr;
+        J.rot = plan.r16 ? a->rot : nullptr;
         return J;
     }
 
     // K jobs (args[0..K)) of identical shapes in one set of launches per wave; the job
     // table is staged through `pinned` (kept alive by the caller until the copy has run)
     int init_batch(const IaSynthArgs *args, int nj, hipStream_t st, XJob *pinned) {
-        int rc = init(&args[0], st);
-        if (rc || nj == 1) return rc;
         IA_ARG(nj <= IA_BATCH_MAX, "ia_synth_levels_batch: too many jobs in one batch");
-        IA_ARG(xw, "ia_synth_levels_batch: batches run the exact matcher on one GPU (fused kernel)");
+        int rc = init(&args[0], st, nj);
+        if (rc || nj == 1) return rc;
+        IA_ARG(plan.xw, "ia_synth_levels_batch: batches run the exact matcher on one GPU (fused kernel)");
         // XJob carries no exchange view: K jobs would publish into one box (cells indexed by
         // query only) and advance its epoch once per wave for K jobs
         IA_ARG(!a->comm && !a->lsh,
                "ia_synth_levels_batch: a batch of K > 1 jobs takes neither a comm nor an LSH index");
-        K = nj;
         part.resize(K - 1);
         for (int k = 1; k < K; ++k) {
             const IaSynthArgs &b = args[k];
@@ -579,9 +615,9 @@ struct LevelRun {
                        !b.dbg_px == !a->dbg_px,
                    "ia_synth_levels_batch: the jobs of a batch must have identical shapes and forms");
             part[k - 1].member = true;
-            if ((rc = part[k - 1].init(&b, st))) return rc;
-            IA_ARG(part[k - 1].xw, "ia_synth_levels_batch: a job without the fused kernel");
-            IA_ARG(part[k - 1].r16 == r16, "ia_synth_levels_batch: jobs with and without the rotated DB");
+            if ((rc = part[k - 1].init(&b, st, K))) return rc;
+            IA_ARG(part[k - 1].plan.xw, "ia_synth_levels_batch: a job without the fused kernel");
+            IA_ARG(part[k - 1].plan.r16 == plan.r16, "ia_synth_levels_batch: jobs with and without the rotated DB");
         }
         pinned[0] = job_entry();
         for (int k = 1; k < K; ++k) pinned[k] = part[k - 1].job_entry();
@@ -598,6 +634,7 @@ struct LevelRun {
         _Float16 *q16s[2] = {ws.q16, ws.q16b};
         double *nqs[2] = {ws.nq, ws.nqb};
         const int b = t & 1;
+        const bool r16 = plan.r16;
         if (t == 0 && (rc = launch_query_wave(B, Bp, 0, y_lo, M, a->center, q64s[0], qps[0], nqs[0],
                                               a->amax, q16s[0], sq, r16 ? a->rot : nullptr)))
             return rc;
@@ -607,81 +644,40 @@ struct LevelRun {
                                         p.a->amax, p.ws.q16, sq, r16 ? p.a->rot : nullptr)))
                 return rc;
         }
-        const XJob *jt = K > 1 ? ws.jtab : nullptr;
-        ImgDb img{};
-        const bool im = a->dbi != nullptr;
-        IA_ARG(!im || img_db_layout(src.A.h, src.A.w, src.A.hs, src.A.ws, 1, a->row0, a->nrows, a->dbi, img,
-                                    nullptr),
-               "ia_synth_level: an image-form DB for a level it does not apply to");
-        IA_ARG(im || a->db, "ia_synth_level: no DB (row form or image form)");
+        const DbView &v = plan.v;
         float *segmin = match_segmin(ws.scratch);
-        hipEvent_t e0 = timed ? prof_event(ev0 + 3 * nscreen) : nullptr;
-        hipEvent_t e1 = timed ? prof_event(ev0 + 3 * nscreen + 1) : nullptr;
+        hipEvent_t e0 = wave_event(0), e1 = wave_event(1);
         if (e0) IA_HIP(hipEventRecord(e0, sq));
-        const StageMap sm = db_stage_map(a->row0, a->nrows, src.A.w, src.A.h);
-        const int form = !im ? XW_ROWS
-                       : (xwave_on() == 2 && sm.W > 0 && xstrip_applies(src)) ? XW_STRIP : XW_IMG;
-        // a compact wave (ia_rot16.h RK_*): the 32-slot screen and the lower-bound exact stage on
-        // the waves without a row-0 or column-0 pixel of one unsharded job's strip-form R16 level
-        const bool rk = r16 && a->dbk && K == 1 && !a->comm && form == XW_STRIP && a->nrows >= compact_min_rows();
-        const bool cmp = rk && wave_compact(W, t);
+        const bool cmp = plan.rk && wave_compact(W, t);
         if (r16) {
-            if ((rc = launch_screen16r(cmp ? a->dbk : a->dbr, a->nrows, sm, q16s[b], M, segmin, sq, jt, K, b, cmp)))
+            if ((rc = launch_screen16r(cmp ? a->dbk : a->dbr, v.nrows, v.sm, q16s[b], M, segmin, sq, xa.jobs, K, b,
+                                       cmp)))
                 return rc;
-        } else if ((rc = launch_screen16(a->db, im ? &img : nullptr, a->nrows, sm, q16s[b], M, segmin, sq, jt,
-                                         K, b, a->comm != nullptr))) {
+        } else if ((rc = launch_screen16(v.db, v.im ? &v.img : nullptr, v.nrows, v.sm, q16s[b], M, segmin, sq,
+                                         xa.jobs, K, b, a->comm != nullptr))) {
             return rc;
         }
         if (e1) IA_HIP(hipEventRecord(e1, sq));
-        int y_lo_n = 0, M_n = 0;
-        if (t + 1 < nw) wave_rows(H, W, t + 1, y_lo_n, M_n);
-        XArgs x{};
-        x.src = src;
-        x.im = img;
-        x.db = a->db;
-        x.row0 = a->row0;
-        x.nrows = a->nrows;
-        x.nseg = db_nsegs(a->nrows);
-        x.seg_rows = db_seg_rows(a->nrows);
-        x.smap = sm;
-        x.segmin = segmin;
+        // the level's arguments (init), and what wave t changes
+        XArgs x = xa;
         x.q64 = q64s[b]; x.qp = qps[b]; x.nq = nqs[b];
-        x.amax = a->amax;
-        x.center = a->center;
         x.q64n = q64s[b ^ 1]; x.qpn = qps[b ^ 1]; x.nqn = nqs[b ^ 1]; x.q16n = q16s[b ^ 1];
-        x.B = B;
-        x.Bp = Bp;
-        x.H = H; x.M = M; x.y_lo_n = y_lo_n; x.M_n = M_n;
-        x.dbox = ws.dbox;
-        x.tickets = ws.ctl;
-        x.err = ws.ctl + XW_CTL_ERR;
-        x.stats = prof ? ws.stats : nullptr;
-        x.f = FinishArgs{t, y_lo, W, a->N_total, a->weights, a->kappa_factor, a->Bp_lg, a->s,
-                         a->im, a->dbg_px, a->dbg_dist, nullptr, nullptr};
-        if (peer) x.f.px = comm_peer_wave(a->comm);
-        x.jobs = jt;
-        x.trace = xw_trace(a->tag);
-        x.rot = r16 ? a->rot : nullptr;
-        x.askc = r16 ? r16_askc(a->dbr, a->nrows) : nullptr;
-        x.rk = rk ? 1 : 0;
+        x.M = M;
+        if (t + 1 < nw) wave_rows(H, W, t + 1, x.y_lo_n, x.M_n);
+        x.f.t = t;
+        x.f.y_lo = y_lo;
+        if (plan.peer) x.f.px = comm_peer_wave(a->comm);
         if (cmp) {
             g_compact_waves.fetch_add(1, std::memory_order_relaxed);
             const char *dbk = reinterpret_cast<const char *>(a->dbk);
-            x.restc = reinterpret_cast<const unsigned char *>(dbk + rk_code_off(a->nrows));
-            x.rmax = reinterpret_cast<const float *>(dbk + rk_rmax_off(a->nrows));
+            x.restc = reinterpret_cast<const unsigned char *>(dbk + rk_code_off(v.nrows));
+            x.rmax = reinterpret_cast<const float *>(dbk + rk_rmax_off(v.nrows));
             x.q16 = q16s[b];
         }
-        const int R = M > y_lo_n + M_n - y_lo ? M : y_lo_n + M_n - y_lo;
-        const int nwg = xsplit_grid(r16 && K == 1 && !a->comm && form == XW_STRIP, a->nrows, R);
-        if (nwg != R) x.xbox = ws.xbox;
-        if ((rc = launch_xwave(x, nwg, form, sq, K))) return rc;
-        if (timed) IA_HIP(hipEventRecord(prof_event(ev0 + 3 * nscreen + 2), sq));
-        ++nscreen;
-        pairs += (double)M * (double)a->nrows * K;
-        if (prof) Ms.push_back(M);
-        static const int sync_every = env_int("IA_SYNC_EVERY", 0);
-        if (sync_every > 0 && t % sync_every == sync_every - 1) IA_HIP(hipStreamSynchronize(sq));
-        return IA_OK;
+        const int R = M > x.y_lo_n + x.M_n - y_lo ? M : x.y_lo_n + x.M_n - y_lo;
+        if (plan.split) x.xbox = ws.xbox;
+        if ((rc = launch_xwave(x, plan.split ? 2 * R : R, plan.variant(K, cmp), sq, K))) return rc;
+        return wave_counted(t, M, sq);
     }
 
     // diagnostic: the sharded path with every shard's exact stage run here, one after the
@@ -692,23 +688,19 @@ struct LevelRun {
             if ((rc = launch_query_wave(B, Bp, t, y_lo, M, a->center, ws.q64, ws.qp, ws.nq,
                                         sim[r].amax, ws.q16, sq)))
                 return rc;
-            const FinishArgs fr{t, y_lo, W, a->N_total, a->weights, a->kappa_factor, a->Bp_lg,
-                                a->s, a->im, a->dbg_px, a->dbg_dist, ws.rec_all + (long)r * M,
-                                ws.coh};
+            const FinishArgs fr = finish_args(t, y_lo, ws.rec_all + (long)r * M, ws.coh);
             if ((rc = launch_match(src, sim[r].row0, sim[r].nrows, sim[r].db, sim[r].dbi, ws.qp, ws.q16, M,
                                    ws.q64, ws.nq, sim[r].amax, ws.scratch, ws.best_local, nullptr,
                                    sq, nullptr, nullptr, &fr)))
                 return rc;
         }
-        const FinishArgs fa{t, y_lo, W, a->N_total, a->weights, a->kappa_factor, a->Bp_lg, a->s,
-                            a->im, a->dbg_px, a->dbg_dist, nullptr, nullptr};
-        k_finish<<<M, 64, 0, sq>>>(src, ws.rec_all, ws.coh, nsim, M, fa);
+        k_finish<<<M, 64, 0, sq>>>(src, ws.rec_all, ws.coh, nsim, M, finish_args(t, y_lo, nullptr, nullptr));
         IA_LAUNCH_CHECK("k_finish");
         return IA_OK;
     }
 
     int done(hipStream_t st) {
-        if (xw) {
+        if (plan.xw) {
             k_err_sticky<<<1, 64, 0, st>>>(ws.ctl, K > 1 ? ws.jtab : nullptr, K);
             IA_HIP(hipGetLastError());
         }
@@ -787,32 +779,20 @@ int ia_diag_set_xwave(int on) {
 }
 
 int ia_level_resources(const IaSynthArgs *a, int *out) {
-    // (compact waves, ia_rot16.h RK_*, are not reported: they run only without a comm, where no
-    // kernel waits for another rank; their k_xstrip<false, true, true> (159 VGPRs against 151, the
-    // same LDS and 3 workgroups per CU) and k_screen16c (less LDS and fewer VGPRs) fit wherever the
-    // forms reported here do; nor is the split tail, k_xstrip<false, true, CMP, true>: 155 / 161
-    // VGPRs, the same LDS and 3 workgroups per CU, also unsharded levels only)
-    // the kernels this level launches per wave, decided as LevelRun::init / xw_wave decide:
-    // out = {waiting kernel LDS bytes, VGPRs; screen LDS bytes, VGPRs} (the forward-progress
-    // rule of DESIGN.md §7, per level: ADVICE r05)
+    // the kernels this level's plan launches per wave (per level: ADVICE r05): out =
+    // {waiting kernel LDS bytes, VGPRs; screen LDS bytes, VGPRs} of the plain one-job variant and
+    // the widest screen instance.  Compact waves and split candidates run only without a comm,
+    // where no kernel waits for another rank, and fit wherever these do (159 and 155 / 161 VGPRs
+    // against 151, the same LDS and 3 workgroups per CU; k_screen16c: less LDS, fewer VGPRs)
     IA_ARG(a && out && a->nrows > 0, "ia_level_resources: bad args");
-    const bool peer = a->comm && comm_peer_mcap(a->comm) > 0;
-    const bool xw = xwave_on() && !a->lsh && (!a->comm || peer) && exact_stage_mode() != 1;
-    const bool r16 = xw && a->dbr && a->rot;
-    const bool im = a->dbi != nullptr;
-    const DbSrc src = make_dbsrc(a->src);
-    const StageMap sm = db_stage_map(a->row0, a->nrows, src.A.w, src.A.h);
-    hipFuncAttributes f{}, sc{};
-    int rc;
-    if (xw) {
-        const int form = !im ? XW_ROWS : (xwave_on() == 2 && sm.W > 0 && xstrip_applies(src)) ? XW_STRIP : XW_IMG;
-        rc = xwave_attributes(form, r16, &f);
-    } else {
-        IA_HIP(hipFuncGetAttributes(&f, reinterpret_cast<const void *>(&k_peer_finish)));
-        rc = IA_OK;
-    }
+    LevelPlan p;
+    int rc = level_plan(*a, 1, false, &p);
     if (rc) return rc;
-    rc = r16 ? screen_resources_r16(&sc) : screen16_attributes(im, &sc);
+    hipFuncAttributes f{}, sc{};
+    if (p.xw) rc = xwave_attributes(XwVariant{p.form, false, p.r16, false, false}, &f);
+    else IA_HIP(hipFuncGetAttributes(&f, reinterpret_cast<const void *>(&k_peer_finish)));
+    if (rc) return rc;
+    rc = p.r16 ? screen_resources_r16(&sc) : screen16_attributes(a->dbi != nullptr, &sc);
     if (rc) return rc;
     out[0] = (int)f.sharedSizeBytes;
     out[1] = f.numRegs;
@@ -858,19 +838,26 @@ int ia_diag_wave_compact(int W, int t) { return wave_compact(W, t) ? 1 : 0; }
 
 long ia_diag_compact_waves(void) { return g_compact_waves.load(std::memory_order_relaxed); }
 
-long ia_diag_set_compact_min_rows(long rows) {
-    const long prev = compact_min_rows();
-    if (rows >= 0) g_compact_min_rows.store(rows > 0 ? rows : LONG_MAX);
+// a row threshold's setter: 0 turns the form off, negative leaves it; the previous value (0: off)
+static long set_min_rows(std::atomic<long> &g, long rows) {
+    const long prev = g.load(std::memory_order_relaxed);
+    if (rows >= 0) g.store(rows > 0 ? rows : LONG_MAX);
     return prev == LONG_MAX ? 0 : prev;
 }
-
-long ia_diag_set_xsplit_min_rows(long rows) {
-    const long prev = xsplit_min_rows();
-    if (rows >= 0) g_xsplit_min_rows.store(rows > 0 ? rows : LONG_MAX);
-    return prev == LONG_MAX ? 0 : prev;
-}
+long ia_diag_set_compact_min_rows(long rows) { return set_min_rows(g_compact_min_rows, rows); }
+long ia_diag_set_xsplit_min_rows(long rows) { return set_min_rows(g_xsplit_min_rows, rows); }
 
 int ia_diag_xsplit_grid(int eligible, long nrows, int R) { return xsplit_grid(eligible != 0, nrows, R); }
+
+int ia_diag_level_plan(const IaSynthArgs *a, int K, int *out) {
+    IA_ARG(a && out && a->nrows > 0 && K >= 1, "ia_diag_level_plan: bad args");
+    LevelPlan p;
+    const int rc = level_plan(*a, K, false, &p);
+    const int f[IA_PLAN_FIELDS] = {p.xw, p.form, p.r16, p.rk, p.split, p.peer, p.fused, p.tail,
+                                   (int)p.v.nseg, p.v.seg_rows, p.v.sm.W > 0};
+    for (int i = 0; i < IA_PLAN_FIELDS && !rc; ++i) out[i] = f[i];
+    return rc;
+}
 
 int ia_release_thread_resources(void) {
     IA_HIP(g_graphs.retire());
@@ -1070,7 +1057,7 @@ static int synth_levels(const IaSynthArgs *levels, int n, int K, void *stream) {
             (rc = run[j].init_batch(&levels[(size_t)j * K], K, g_pipe.stream(j), pinned + (size_t)j * K)))
             return rc;
         // (on the fused path wave t's launch also builds wave t + 1's query rows)
-        pl[j] = PipeLevel{run[j].H, run[j].W, run[j].xw, multi_rank(j)};
+        pl[j] = PipeLevel{run[j].H, run[j].W, run[j].plan.xw, multi_rank(j)};
     }
     // enqueue order (IA_PIPE_ORDER): 0 [default] the finest level first, coarse waves just
     // ahead of their need; 1 every level whole, coarse to fine.  One host thread enqueues

@@ -267,7 +267,7 @@ __device__ __forceinline__ double xw_finish(const XArgs &a, int i, int y, int x,
 // step 5 (wave 0): the query row of (y, x + 1) for wave t + 1 (k_query_wave's arithmetic):
 // the prefetched features (nxw, LDS-DMA words), this pixel's new value own (dep 1) or the
 // upper neighbour's decision (dep 2, ticket i - 1 of this launch)
-// rotl (nullable): an R16 level's rotation in LDS (k_xstrip<.., true>): the query row in the
+// rotl (nullable): an R16 level's rotation in LDS (k_xstrip with ROT):the query row in the
 // R16 layout (ia_rot16.h) and q64 slot 55 = |kappa_skip|^2; dq: 64 doubles of LDS scratch
 __device__ __forceinline__ void xw_next_query(const XArgs &a, int i, int y, int x, int lane, int dep, double own,
                                               float amx, const unsigned (*nxw)[64],
@@ -1197,7 +1197,7 @@ __device__ __forceinline__ void sync3(unsigned *cnt, unsigned g, int lane) {
 
 // ROT: an R16 level (ia_rot16.h): the exact stage's bound eps_R, and the next query row
 // rotated (the rotation copied into LDS by wave 0 at the start)
-// workgroups per CU the batch form (k_xstrip<true>) is built for (A/B builds)
+// workgroups per CU the batch form (k_xstrip with BATCH) is built for (A/B builds)
 #ifndef IA_XSTRIP_BOCC
 #define IA_XSTRIP_BOCC 4
 #endif
@@ -1787,13 +1787,67 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
 
 }  // namespace ia
 
+namespace ia {
+
+// the table of built instances (k_xstrip's static_asserts name the combinations that are not:
+// compact waves and split candidates are one job's, with the rotation)
+const void *xwave_kernel(XwVariant v) {
+    static const struct { XwVariant v; const void *f; } built[] = {
+        {{XW_STRIP, false, true, false, false}, (const void *)&k_xstrip<false, true>},
+        {{XW_STRIP, false, false, false, false}, (const void *)&k_xstrip<false, false>},
+        {{XW_IMG, false, false, false, false}, (const void *)&k_xwave<true, false>},
+        {{XW_ROWS, false, false, false, false}, (const void *)&k_xwave<false, false>},
+        {{XW_STRIP, false, true, true, true}, (const void *)&k_xstrip<false, true, true, true>},
+        {{XW_STRIP, false, true, false, true}, (const void *)&k_xstrip<false, true, false, true>},
+        {{XW_STRIP, false, true, true, false}, (const void *)&k_xstrip<false, true, true>},
+        {{XW_STRIP, true, true, false, false}, (const void *)&k_xstrip<true, true>},
+        {{XW_STRIP, true, false, false, false}, (const void *)&k_xstrip<true, false>},
+        {{XW_IMG, true, false, false, false}, (const void *)&k_xwave<true, true>},
+        {{XW_ROWS, true, false, false, false}, (const void *)&k_xwave<false, true>},
+    };
+    if (v.form != XW_STRIP) v.rot = false;   // (k_xwave takes the R16 bound at run time)
+    for (const auto &e : built)
+        if (e.v.form == v.form && e.v.batch == v.batch && e.v.rot == v.rot && e.v.cmp == v.cmp && e.v.split == v.split)
+            return e.f;
+    set_error("xwave_kernel: this instance of the fused kernel is not built");
+    return nullptr;
+}
+
+int xwave_attributes(XwVariant v, hipFuncAttributes *at) {
+    const void *f = xwave_kernel(v);
+    if (!f) return IA_E_ARG;
+    IA_HIP(hipFuncGetAttributes(at, f));
+    return IA_OK;
+}
+
+int launch_xwave(const XArgs &a, int nblocks, XwVariant v, hipStream_t st, int njobs) {
+    if (nblocks <= 0) return IA_OK;
+    IA_ARG(njobs >= 1 && njobs <= IA_BATCH_MAX && v.batch == (njobs > 1) && (!v.batch || a.jobs),
+           "launch_xwave: bad batch");
+    IA_ARG(v.form != XW_STRIP || (a.smap.W > 0 && xstrip_applies(a.src) && a.seg_rows >= 128 && a.seg_rows <= 512),
+           "launch_xwave: the strip form needs a strip-order image-form level");
+    IA_ARG(v.form != XW_STRIP || v.rot == (a.rot != nullptr), "launch_xwave: the strip form and its rotation disagree");
+    IA_ARG(v.cmp == (a.restc != nullptr) && (!v.cmp || (RK_BUILT && a.rmax && a.q16)),
+           "launch_xwave: a compact wave is one job of an R16 strip level");
+    IA_ARG(v.split == (a.xbox != nullptr) && (!v.split || (!a.f.px.nranks && a.nseg <= XS_SEG_MASK + 1)),
+           "launch_xwave: split candidates are for one unsharded job of an R16 strip level");
+    const void *f = xwave_kernel(v);
+    if (!f) return IA_E_ARG;
+    void *args[] = {const_cast<XArgs *>(&a)};   // (split: nblocks = two workgroups per pixel, helper and owner)
+    (void)hipLaunchKernel(f, dim3((unsigned)nblocks, (unsigned)njobs), dim3(256), args, 0, st);
+    IA_LAUNCH_CHECK("k_xwave");
+    return IA_OK;
+}
+
+}  // namespace ia
+
 /* the fused strip kernel's resources (DESIGN.md §7 forward-progress rule): rot 1 the R16
  * form; LDS bytes per workgroup, VGPRs per lane */
 extern "C" int ia_fused_resources(int rot, int *lds, int *vgprs) {
     IA_ARG(lds && vgprs, "ia_fused_resources: bad args");
     hipFuncAttributes at{};
-    if (rot) IA_HIP(hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&ia::k_xstrip<false, true>)));
-    else IA_HIP(hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&ia::k_xstrip<false, false>)));
+    const int rc = ia::xwave_attributes(ia::XwVariant{ia::XW_STRIP, false, rot != 0, false, false}, &at);
+    if (rc) return rc;
     *lds = (int)at.sharedSizeBytes;
     *vgprs = at.numRegs;
     return IA_OK;
@@ -1806,53 +1860,3 @@ extern "C" int ia_diag_xsplit_counts(unsigned long long *out) {
                                hipMemcpyDeviceToHost));
     return IA_OK;
 }
-
-namespace ia {
-
-// the one-job fused kernel of a form (launch_xwave): k_xstrip<false, rot> (XW_STRIP),
-// k_xwave<true / false, false> (XW_IMG / XW_ROWS)
-int xwave_attributes(int form, bool rot, hipFuncAttributes *at) {
-    const void *f = form == XW_STRIP ? (rot ? reinterpret_cast<const void *>(&k_xstrip<false, true>)
-                                            : reinterpret_cast<const void *>(&k_xstrip<false, false>))
-                    : form == XW_IMG ? reinterpret_cast<const void *>(&k_xwave<true, false>)
-                                     : reinterpret_cast<const void *>(&k_xwave<false, false>);
-    IA_HIP(hipFuncGetAttributes(at, f));
-    return IA_OK;
-}
-
-int launch_xwave(const XArgs &a, int nblocks, int form, hipStream_t st, int njobs) {
-    if (nblocks <= 0) return IA_OK;
-    IA_ARG(njobs >= 1 && njobs <= IA_BATCH_MAX && (njobs == 1 || a.jobs), "launch_xwave: bad batch");
-    IA_ARG(form != XW_STRIP || (a.smap.W > 0 && xstrip_applies(a.src) && a.seg_rows >= 128 && a.seg_rows <= 512),
-           "launch_xwave: the strip form needs a strip-order image-form level");
-    const dim3 grid((unsigned)nblocks, (unsigned)njobs);
-    const bool b = njobs > 1;
-    IA_ARG(!a.restc || (RK_BUILT && form == XW_STRIP && a.rot && !b && a.rmax && a.q16),
-           "launch_xwave: a compact wave is one job of an R16 strip level");
-    IA_ARG(!a.xbox || (form == XW_STRIP && a.rot && !b && !a.f.px.nranks && a.nseg <= XS_SEG_MASK + 1),
-           "launch_xwave: split candidates are for one unsharded job of an R16 strip level");
-    if (form == XW_STRIP) {
-        if (a.xbox) {   // nblocks = two workgroups per pixel (helper, owner)
-            if (a.restc) k_xstrip<false, true, true, true><<<grid, 256, 0, st>>>(a);
-            else k_xstrip<false, true, false, true><<<grid, 256, 0, st>>>(a);
-        } else if (a.restc) {
-            k_xstrip<false, true, true><<<grid, 256, 0, st>>>(a);
-        } else if (a.rot) {
-            if (b) k_xstrip<true, true><<<grid, 256, 0, st>>>(a);
-            else k_xstrip<false, true><<<grid, 256, 0, st>>>(a);
-        } else {
-            if (b) k_xstrip<true, false><<<grid, 256, 0, st>>>(a);
-            else k_xstrip<false, false><<<grid, 256, 0, st>>>(a);
-        }
-    } else if (form == XW_IMG) {
-        if (b) k_xwave<true, true><<<grid, 256, 0, st>>>(a);
-        else k_xwave<true, false><<<grid, 256, 0, st>>>(a);
-    } else {
-        if (b) k_xwave<false, true><<<grid, 256, 0, st>>>(a);
-        else k_xwave<false, false><<<grid, 256, 0, st>>>(a);
-    }
-    IA_LAUNCH_CHECK("k_xwave");
-    return IA_OK;
-}
-
-}  // namespace ia

@@ -68,6 +68,19 @@ long ia_diag_compact_waves(void);
 long ia_diag_set_xsplit_min_rows(long rows);
 int ia_diag_xsplit_grid(int eligible, long nrows, int R);
 int ia_diag_xsplit_counts(unsigned long long *out);
+/* what level a's arguments and this process's knobs select for a level of K jobs sharing its
+ * launches, as ia_synth_level(s) would decide it now: out[IA_PLAN_FIELDS] = {fused per-wave kernel
+ * 0 / 1, its form (0 k_xwave on rows, 1 k_xwave on the image form, 2 k_xstrip; -1 without),
+ * R16 screen, compact waves, two workgroups per pixel, device-side exchange, fused tail,
+ * the tail without the fused kernel (0 the exact stage's own, 1 k_peer_finish, 2 k_lsh_tail,
+ * 3 k_finish_gather, 4 k_finish), segments, rows per segment, strip order 0 / 1}.  Reads only the
+ * arguments; touches no device when a->comm is NULL.
+ * The knobs that decide it (ia_diag_set_xwave, _rescore_mode, _compact_min_rows,
+ * _xsplit_min_rows) are sampled ONCE per level, when its synthesis call starts: a setter called
+ * meanwhile changes the levels started after it, never the form of a level under way.  (Apart from this plan, the
+ * unfused matcher picks k_rescore or the work list by _rescore_mode wave by wave: same results.) */
+#define IA_PLAN_FIELDS 11
+int ia_diag_level_plan(const IaSynthArgs *a, int K, int *out);
 /* exact stage form for this process: 0 one workgroup per query (k_rescore), 1 the work list
  * (k_select / k_items / k_gather), -1 the default (work list above 2^20 rows); other values
  * leave it; returns the previous value */

@@ -38,7 +38,7 @@ def counts():
 # ---- host ----------------------------------------------------------------------------------------
 
 def test_grid_is_doubled_only_where_the_switch_applies(xsplit):
-    """ia_diag_xsplit_grid (the rule xw_wave launches by): 2 R workgroups on an eligible level of
+    """ia_diag_xsplit_grid (the rule level_plan decides a level's split by): 2 R workgroups on an eligible level of
     at least the threshold's rows, R below it, with the switch off and on any other level;
     ia_diag_set_xsplit_min_rows reports the threshold in force (0: off); the wave geometry and
     the pipeline's schedule do not depend on the switch."""
@@ -110,6 +110,55 @@ def test_split_synthesis_equals_oracle_and_split_off(gpu, xsplit, monkeypatch, s
                     assert np.array_equal(got[l][0], ref[l][0]), l
     finally:
         lib.ia_diag_set_compact_min_rows(prev)
+
+
+# ---- the reported plan is what runs ---------------------------------------------------------------
+
+@pytest.mark.gpu
+def test_level_plan_reports_what_runs_and_is_sampled_per_level(gpu, xsplit, monkeypatch):
+    """The finest (strip-order, R16) level of the small synthesis above with both thresholds at 1:
+    ia_diag_level_plan says compact waves and split candidates, and running the level advances
+    both forms' counters.  ia_diag_set_xwave(1) after the arguments are built changes the NEXT
+    call of the same arguments to k_xwave on the image form (the knobs are sampled when a level
+    starts): the plan says so and neither counter moves."""
+    import algorithms
+    import image_analogies as ia
+    import _ia
+    from test_gpu_split16 import dev
+    lib = _ia.lib()
+    monkeypatch.setenv('IA_ROT_MIN_ROWS', '1')
+    A, Aps, B = analogy_inputs(57, (128, 128), (37, 41), n_ap=1)
+    A_pyr, Ap_list, B_pyr, Bp_pyr, L = o.setup_luminance(A, Aps, B, cap=2, seed=57)
+    prev_compact, prev_xwave = lib.ia_diag_set_compact_min_rows(-1), lib.ia_diag_set_xwave(-1)
+    try:
+        lib.ia_diag_set_compact_min_rows(1)
+        xsplit(1)
+        lib.ia_diag_set_xwave(2)
+        index = algorithms.level_index([dev(p) for p in A_pyr], [[dev(p) for p in q] for q in Ap_list], L - 1, rot=True)
+        assert index.dbr is not None and index.dbk is not None
+        Bp = [dev(b) for b in Bp_pyr]
+        call = ia._LevelCall(L - 1, L, index, dev(B_pyr[L - 2]), dev(B_pyr[L - 1]), Bp[L - 2], Bp[L - 1],
+                             _ia.to_dev(o.compute_weights(3, 5, 12, 1)), 0.5)
+        run = lambda: _ia.check(lib.ia_synth_level(ctypes.byref(call.args), _ia.stream()), 'ia_synth_level')  # noqa: E731
+        plan = _ia.level_plan(call.args)
+        print('plan:', plan)
+        assert plan['xw'] and plan['form'] == _ia.XW_STRIP and plan['r16'] and plan['strips']
+        assert plan['rk'] and plan['split'] and plan['fused'] and not plan['peer']
+        n0, c0 = lib.ia_diag_compact_waves(), counts()
+        run()
+        dn, dc = lib.ia_diag_compact_waves() - n0, counts() - c0
+        print('as planned: compact waves %d, helper pixels %d' % (dn, dc[0]))
+        assert dn > 0 and dc[0] > 0
+        lib.ia_diag_set_xwave(1)
+        plan = _ia.level_plan(call.args)
+        assert plan['xw'] and plan['form'] == _ia.XW_IMG and not plan['rk'] and not plan['split']
+        n0, c0 = lib.ia_diag_compact_waves(), counts()
+        run()
+        assert lib.ia_diag_compact_waves() == n0 and not (counts() - c0).any()
+        _ia.sched_status()
+    finally:
+        lib.ia_diag_set_compact_min_rows(prev_compact)
+        lib.ia_diag_set_xwave(prev_xwave)
 
 
 # ---- ties and shares -----------------------------------------------------------------------------

@@ -786,6 +786,109 @@ def test_residency_rule_takes_each_levels_own_kernels():
     assert ia.sharded_schedule(two, True, 1, [xstrip, xwave], [screen, screen]) is False
 
 
+# ---- what a level's arguments and knobs select (csrc/ia_synth.hip level_plan) ----------------
+
+def level_plan_restated(Ah, Aw, row0, nrows, K, has, knobs):
+    """The rules of level_plan / db_view for an unsharded level of one A' image set at the default
+    chunk target, restated (a cross-check of the library's only: test_level_plan_table).  has: the
+    non-null pointers among db, dbi, dbr, rot, dbk, lsh; knobs: xwave, rescore, compact and xsplit
+    (row thresholds, 0: off).  None where the library refuses the arguments."""
+    want = -(-nrows // (512 * 128))
+    tpw = 1
+    while tpw < want and tpw < 64:
+        tpw *= 2
+    ch = 128 * tpw
+    padded = -(-(-(-nrows // ch)) // 4) * 4 * ch
+    seg_rows = min(ch, 512)
+    nseg = padded // seg_rows
+    sc = ch // 128
+    whole = padded == nrows
+    img_ok = Aw % 128 == 0 and row0 % 128 == 0 and whole and row0 + nrows < 2 ** 31
+    strips = (Aw % 128 == 0 and row0 % Aw == 0 and nrows % Aw == 0 and whole and
+              (nrows // Aw) % sc == 0 and (row0 // Aw) % sc == 0 and Ah % sc == 0)
+    lsh = 'lsh' in has
+    xw = knobs['xwave'] != 0 and not lsh and knobs['rescore'] != 1
+    plan = dict(xw=int(xw), form=-1, r16=int(xw and 'dbr' in has and 'rot' in has), rk=0, split=0, peer=0,
+                fused=int(not lsh), tail=2 if lsh else 0, nseg=0, seg_rows=0, strips=0)
+    if lsh:
+        return plan
+    if not ('db' in has or 'dbi' in has) or ('dbi' in has and not img_ok):
+        return None
+    plan.update(nseg=nseg, seg_rows=seg_rows, strips=int(strips))
+    if not xw:
+        return plan
+    strip_kernel = Aw >= 128 and Aw % 2 == 0       # (the coarse A is half as wide: the test's levels)
+    plan['form'] = 0 if 'dbi' not in has else 2 if knobs['xwave'] == 2 and strips and strip_kernel else 1
+    one = plan['r16'] and K == 1 and plan['form'] == 2
+    plan['rk'] = int(bool(one and 'dbk' in has and 0 < knobs['compact'] <= nrows))
+    plan['split'] = int(bool(one and 0 < knobs['xsplit'] <= nrows and nseg <= 2 ** 20))
+    return plan
+
+
+def test_level_plan_table():
+    """ia_diag_level_plan (what ia_synth_level decides once per level) against the
+    rules restated above and against the forms each case is known to take: c4's finest level takes
+    the strip kernel with the R16 screen, compact waves and split candidates; a batch or a missing
+    compact DB does not; the thresholds, ia_diag_set_xwave, the rescore mode and an LSH index each
+    change what they are documented to.  No device is touched (comm = NULL, dummy pointers)."""
+    import _ia
+    lib = _ia.lib()
+    P = 0x1000      # a non-null pointer: the plan only tests these for null-ness
+    lsh = _ia.IaLsh()
+
+    def args(Ah, Aw, row0, nrows, has):
+        a = _ia.IaSynthArgs()
+        a.src.Ah, a.src.Aw, a.src.A_hs, a.src.A_ws, a.src.nAp = Ah, Aw, (Ah + 1) // 2, (Aw + 1) // 2, 1
+        a.row0, a.nrows, a.N_total = row0, nrows, Ah * Aw
+        for name in has:
+            if name == 'lsh':
+                a.lsh = ctypes.pointer(lsh)
+            else:
+                setattr(a, name, P)
+        return a
+
+    full = ('db', 'dbi', 'dbr', 'rot', 'dbk')
+    big, mid = (2048, 2048, 0, 1 << 22), (1024, 1024, 0, 1 << 20)
+    T = 1 << 22     # the default thresholds
+    base = dict(xwave=2, rescore=-1, compact=T, xsplit=T)
+    ROWS, IMG, STRIP = _ia.XW_ROWS, _ia.XW_IMG, _ia.XW_STRIP
+    cases = [   # (level, pointers, K, knobs, expected subset or None: IA_E_ARG)
+        (big, full, 1, {}, dict(xw=1, form=STRIP, r16=1, rk=1, split=1, strips=1)),
+        (big, full, 2, {}, dict(form=STRIP, r16=1, rk=0, split=0)),
+        (big, full[:4], 1, {}, dict(form=STRIP, r16=1, rk=0, split=1)),
+        (mid, full[:4], 1, {}, dict(form=STRIP, r16=1, rk=0, split=0)),
+        (mid, full, 1, dict(compact=1, xsplit=1), dict(form=STRIP, r16=1, rk=1, split=1)),
+        ((256, 256, 128, 32768), ('dbi',), 1, {}, dict(xw=1, form=IMG, strips=0, r16=0)),
+        (big, ('db',), 1, {}, dict(xw=1, form=ROWS, rk=0, split=0)),
+        ((192, 192, 0, 36864), ('dbi',), 1, {}, None),
+        (big, full, 1, dict(xwave=1), dict(xw=1, form=IMG, r16=1, rk=0, split=0)),
+        (big, full, 1, dict(xwave=0), dict(xw=0, form=-1, fused=1, tail=_ia.TAIL_FUSED)),
+        (big, full, 1, dict(rescore=1), dict(xw=0, form=-1)),
+        (big, full + ('lsh',), 1, {}, dict(xw=0, fused=0, tail=_ia.TAIL_LSH)),
+    ]
+    setters = dict(xwave=lib.ia_diag_set_xwave, rescore=lib.ia_diag_set_rescore_mode,
+                   compact=lib.ia_diag_set_compact_min_rows, xsplit=lib.ia_diag_set_xsplit_min_rows)
+    prev = {k: setters[k](-2) for k in setters}      # (-2: every setter leaves its knob)
+    try:
+        for level, has, K, change, expect in cases:
+            knobs = dict(base, **change)
+            for k, v in knobs.items():
+                setters[k](v)
+            a = args(*level, has)
+            restated = level_plan_restated(level[0], level[1], level[2], level[3], K, has, knobs)
+            if expect is None:
+                out = (ctypes.c_int * len(_ia.PLAN_KEYS))()
+                assert restated is None
+                assert lib.ia_diag_level_plan(ctypes.byref(a), K, out) == _ia.IA_E_ARG
+                continue
+            got = _ia.level_plan(a, K)
+            assert got == restated, (level, has, K, change)
+            assert {k: got[k] for k in expect} == expect, (level, has, K, change)
+    finally:
+        for k, v in prev.items():
+            setters[k](v)
+
+
 # ---- multi-GPU from the package API (gloo, 2 ranks; the device calls are faked) -------------
 
 def test_rank_jobs_partition_and_bench_seeds():
