@@ -122,6 +122,8 @@ _SIGS = {
     'ia_synth_level3': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), _dp]),
     'ia_synth3_status': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.c_int, _dp]),
     'ia_synth_levels3': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.c_int, _dp]),
+    'ia_synth_levels3_batch': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.c_int, ctypes.c_int,
+                                              _dp]),
     'ia_db3_rot_bytes': (ctypes.c_size_t, [ctypes.c_long]),
     'ia_db3_rot_components': (ctypes.c_int, []),
     'ia_db3_rot_floats': (ctypes.c_int, []),

@@ -19,7 +19,9 @@
 // pick over the causal 3x5 window, kappa test, s / im and the debug record) is the tail core
 // of ia_finish.h, shared with the luminance kernels (c3_window, c3_decide); the kernels here
 // add the 165-term distances and the B' store of all three channels.  ia_synth_levels3 runs
-// the levels pipelined.  Single GPU, exact matcher.
+// the levels pipelined; ia_synth_levels3_batch runs K jobs of identical shapes with the job as
+// a grid dimension of the R16c wave's launches (k_query3rb, k_screen3rb, k_exact3b: the same
+// bodies, per-job pointers from a device job table).  Single GPU, exact matcher.
 #include "ia_common.h"
 #include "ia_internal.h"
 #include "ia_finish.h"
@@ -699,12 +701,14 @@ __device__ __forceinline__ void r3_query(int m, int M, int k, double v, const Co
     }
 }
 
-// queries of wave t for the R16c screen (as k_query3s; qin: caller-given rows, diagnostics)
-__global__ __launch_bounds__(256) void k_query3r(Img3 Bsm, Img3 Blg, Img3 Bpsm, Img3 Bplg, int t,
-                                                 int y_lo, int M, const Col16Meta *__restrict__ meta,
-                                                 const float *__restrict__ rot, const double *__restrict__ qin,
-                                                 double *__restrict__ q3, double *__restrict__ qn,
-                                                 double *__restrict__ nsk, half8 *__restrict__ q16) {
+// queries of wave t for the R16c screen (as k_query3s; qin: caller-given rows, diagnostics):
+// the body of k_query3r (one job, by-value arguments) and k_query3rb (a batch, job table)
+__device__ __forceinline__ void query3r_body(const Img3 &Bsm, const Img3 &Blg, const Img3 &Bpsm,
+                                             const Img3 &Bplg, int t, int y_lo, int M,
+                                             const Col16Meta *__restrict__ meta,
+                                             const float *__restrict__ rot, const double *__restrict__ qin,
+                                             double *__restrict__ q3, double *__restrict__ qn,
+                                             double *__restrict__ nsk, half8 *__restrict__ q16) {
     __shared__ double red[4];
     __shared__ double ds[D3];
     const int m = blockIdx.x, k = threadIdx.x;
@@ -721,16 +725,24 @@ __global__ __launch_bounds__(256) void k_query3r(Img3 Bsm, Img3 Blg, Img3 Bpsm, 
     }
     r3_query(m, M, k, v, meta, rot, qn, nsk, q16, ds, red);
 }
+__global__ __launch_bounds__(256) void k_query3r(Img3 Bsm, Img3 Blg, Img3 Bpsm, Img3 Bplg, int t,
+                                                 int y_lo, int M, const Col16Meta *__restrict__ meta,
+                                                 const float *__restrict__ rot, const double *__restrict__ qin,
+                                                 double *__restrict__ q3, double *__restrict__ qn,
+                                                 double *__restrict__ nsk, half8 *__restrict__ q16) {
+    query3r_body(Bsm, Blg, Bpsm, Bplg, t, y_lo, M, meta, rot, qin, q3, qn, nsk, q16);
+}
 
 // the R16c screen: as k_screen3 with 11 operand groups per tile and 11 MFMAs per (row tile,
 // query tile); up to 8 query tiles staged per workgroup (a c3 wave's 213 queries: one group,
 // each DB tile read once per wave)
 // 7 query tiles per group (a c3 wave's <= 213 queries: one group; LDS 77 KiB, two workgroups
 // per CU: the grid's ~450 workgroups in one round instead of two)
+// (screen3r_body: the body of k_screen3r, one job, and k_screen3rb, a batch)
 constexpr int S3R_QG = 7;
-__global__ __launch_bounds__(256, 2) void k_screen3r(const half8 *__restrict__ db16, int ntiles,
-                                                     const half8 *__restrict__ q16, int M, int tpw,
-                                                     float *__restrict__ smin) {
+__device__ __forceinline__ void screen3r_body(const half8 *__restrict__ db16, int ntiles,
+                                              const half8 *__restrict__ q16, int M, int tpw,
+                                              float *__restrict__ smin) {
     __shared__ half8 qsh[S3R_QG * R3_TILE];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int qt0 = blockIdx.y * S3R_QG;
@@ -785,10 +797,17 @@ __global__ __launch_bounds__(256, 2) void k_screen3r(const half8 *__restrict__ d
         for (int c = 0; c < R3_MFMA; ++c) a[c] = n[c];
     }
 }
-static inline dim3 screen3r_grid(int ntiles, int M, int &tpw) {
+__global__ __launch_bounds__(256, 2) void k_screen3r(const half8 *__restrict__ db16, int ntiles,
+                                                     const half8 *__restrict__ q16, int M, int tpw,
+                                                     float *__restrict__ smin) {
+    screen3r_body(db16, ntiles, q16, M, tpw, smin);
+}
+// the grid: row tiles per wave (tpw) so that about 512 workgroups cover the (row tile, query
+// group, job) triples of the whole launch (K jobs: grid z); the tile minima do not depend on tpw
+static inline dim3 screen3r_grid(int ntiles, int M, int &tpw, int K = 1) {
     const int QG = ((M + 31) / 32 + S3R_QG - 1) / S3R_QG;
-    tpw = (int)std::max(1L, ((long)ntiles * QG + 4L * 512 - 1) / (4L * 512));
-    return dim3((unsigned)((ntiles + 4 * tpw - 1) / (4 * tpw)), (unsigned)QG);
+    tpw = (int)std::max(1L, ((long)ntiles * QG * K + 4L * 512 - 1) / (4L * 512));
+    return dim3((unsigned)((ntiles + 4 * tpw - 1) / (4 * tpw)), (unsigned)QG, (unsigned)K);
 }
 
 // eps of the R16c screen: u (850 A|q'| + 60 A^2) + 2^-9 1.01 A_skip |kappa_skip|
@@ -1004,223 +1023,81 @@ __device__ __forceinline__ unsigned long long c3_gran(unsigned tag, unsigned bit
     return ((unsigned long long)tag << 32) | bits;
 }
 
+//
+// A batch of K identical-shape jobs (k_exact3b, grid (pixels, jobs)) runs the same body
+// per job: the ticket counters, the error word and the decision granules live in each job's
+// own workspace, so a workgroup of job k takes its pixel from job k's counter and waits only
+// for job k's ticket m - 1, which a workgroup that is already resident took.  The single
+// job's forward-progress argument therefore holds for any dispatch order of the (pixels x
+// jobs) grid: in every job the resident workgroup with the lowest unfinished ticket waits for
+// nothing that is not resident.  A wait that times out sets that job's error word
+// (ia_synth3_status reads every job's).  The batch form also zeroes the padding columns
+// [M_n, roundup32(M_n)) of the next wave's query tiles (the workgroup of its first row).
+// The body is ia_color3_exact.inc, included by both kernels (C3X_M, C3X_YN, C3X_MN: the wave's
+// M, y_lo_n, M_n: nx's own in the single job's kernel, launch arguments in the batch's, whose
+// nx is read in place from the job table).
 template <bool FUSE>
 __global__ __launch_bounds__(256) void k_exact3(Fin3 f, Scr3 sc, Nx3 nx) {
-    __shared__ double qs[D3P], wsh[D3P];
-    __shared__ double ownv[3], nbv[3], qred[4], qds[D3];
-    __shared__ int tks, anydep;
-    __shared__ Acc8 acc[32 * 8];                // a tile's rows (32 x 8 parts)
-    __shared__ Acc8 cacc[15 * 8];               // the coherence rows
-    __shared__ double sump[15], sumw[15];
-    __shared__ long long rix[15];
-    __shared__ int rpos[15][3];
-    __shared__ double rd[4], rw[4];
-    __shared__ long long ri[4];
-    __shared__ float fmn[4];
-    __shared__ int clist[C3_CAND], ccount;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int m = blockIdx.x;
-    if constexpr (FUSE) {
-        if (tid == 0) {
-            tks = (int)atomicAdd(&nx.tickets[f.t & 1], 1u);
-            anydep = 0;
-        }
-        __syncthreads();
-        m = tks;
-        if (m == 0 && tid == 0) __hip_atomic_store(&nx.tickets[(f.t + 1) & 1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const int ro = tid >> 3, j = tid & 7;
-    const int y = f.y_lo + m, x = f.t - 3 * y;
-    const int W = f.W;
-    const bool cur = !FUSE || m < nx.M;
-    const bool nxt = FUSE && y >= nx.y_lo_n && y < nx.y_lo_n + nx.M_n;
-    // FUSE: feature tid of the next query (y, x + 1): loaded now unless it is a wave-t sample
-    double nv = 0.0;
-    int dep = 0, dch = 0;
-    if (FUSE && nxt && tid < D3) {
-        const int X = x + 1;
-        if (tid < D3_FULL) {
-            nv = feat3(nx.Bsm, nx.Blg, y, X, tid);
-        } else if (tid < D3_FULL + 27) {
-            nv = feat3(nx.Bpsm, nx.Bplg, y, X, tid - D3_FULL);
-        } else {
-            const int t2 = (tid - D3_FULL - 27) / 3;
-            dch = (tid - D3_FULL - 27) - 3 * t2;
-            const int rr = symi2(y + t2 / 5 - 2, nx.H), cc = symi2(X + t2 % 5 - 2, W);
-            dep = (rr == y && cc == x) ? 1 : (rr == y - 1 && cc == x + 3) ? 2 : 0;
-            if (dep == 0) nv = nx.Bplg.p[((long)rr * W + cc) * 3 + dch];
-        }
-        if (dep == 2) anydep = 1;
-    }
-    if (cur) {
-    // ---- one round trip: query, weights, coherence s / im, tile minima
-    if (tid < D3P) {
-        qs[tid] = f.q3[(long)m * D3P + tid];
-        wsh[tid] = tid < D3 ? f.weights[tid] : 0.0;
-    }
-    if (tid < 15) c3_window(tid, y, x, f, rix, rpos);
-    const int stride = c3_stride(sc.ntiles);
-    const float4 *sm4 = reinterpret_cast<const float4 *>(sc.smin + (long)m * stride);
-    const int n4 = stride / 4;
-    float4 v[C3_REG];
-#pragma unroll
-    for (int q = 0; q < C3_REG; ++q) {
-        const int i = tid + 256 * q;
-        v[q] = sm4[i < n4 ? i : 0];
-    }
-    auto masked = [&](float4 xx, int i) {   // +inf past the tiles (and the float4 pad)
-        const int b = 4 * i;
-        xx.x = b + 0 < sc.ntiles && i < n4 ? xx.x : INFINITY;
-        xx.y = b + 1 < sc.ntiles && i < n4 ? xx.y : INFINITY;
-        xx.z = b + 2 < sc.ntiles && i < n4 ? xx.z : INFINITY;
-        xx.w = b + 3 < sc.ntiles && i < n4 ? xx.w : INFINITY;
-        return xx;
-    };
-    float mn = INFINITY;
-#pragma unroll
-    for (int q = 0; q < C3_REG; ++q) {
-        v[q] = masked(v[q], tid + 256 * q);
-        mn = fminf(mn, fminf(fminf(v[q].x, v[q].y), fminf(v[q].z, v[q].w)));
-    }
-    for (int i = tid + 256 * C3_REG; i < n4; i += 256) {
-        const float4 xx = masked(sm4[i], i);
-        mn = fminf(mn, fminf(fminf(xx.x, xx.y), fminf(xx.z, xx.w)));
-    }
-    for (int o = 32; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o));
-    if (lane == 0) fmn[wv] = mn;
-    if (tid == 0) ccount = 0;
-    __syncthreads();
-    // ---- the candidate tiles
-    mn = fminf(fminf(fmn[0], fmn[1]), fminf(fmn[2], fmn[3]));
-    bool full;
-    const float amax = __uint_as_float(sc.meta->amax_bits);
-    const double Tseg = sc.nsk ? c3_tseg(mn, amax, sc.qn[m], full, __uint_as_float(sc.rmeta->askip_bits), sc.nsk[m])
-                               : c3_tseg(mn, amax, sc.qn[m], full);
-    if (!full) {
-        auto pick = [&](float4 xx, int i) {
-            const float e4[4] = {xx.x, xx.y, xx.z, xx.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if ((double)e4[e] <= Tseg) {
-                    const int c = atomicAdd(&ccount, 1);
-                    if (c < C3_CAND) clist[c] = 4 * i + e;
-                }
-        };
-#pragma unroll
-        for (int q = 0; q < C3_REG; ++q) pick(v[q], tid + 256 * q);
-        for (int i = tid + 256 * C3_REG; i < n4; i += 256) pick(masked(sm4[i], i), i);
-    }
-    __syncthreads();
-    const int nc = ccount;
-    full = full || nc > C3_CAND;
-    const int ntl = full ? sc.ntiles : nc;
-    if (tid == 0 && sc.stats) {
-        atomicAdd(&sc.stats[0], (unsigned long long)ntl);
-        if (full) atomicAdd(&sc.stats[1], 1ull);
-    }
-    // ---- every row of the candidate tiles (and, with the first, the coherence rows)
-    double bd = INFINITY, bw = 0.0;
-    long long bi = 0x7fffffffffffffffLL;
-    const int nit = ntl > 0 ? ntl : 1;
-    for (int b = 0; b < nit; ++b) {
-        Acc8 ta{}, ca{};
-        const long r0 = ntl > 0 ? (long)(full ? b : clist[b]) * 32 : 0;
-        const long r = r0 + ro < sc.nrows ? r0 + ro : sc.nrows - 1;   // (rows past nrows: not taken)
-        if (ntl > 0) ta = acc8_row(f.db3 + r * D3P, j, qs, wsh);
-        if (b == 0 && tid < 15 * 8) {
-            const long long ix = rix[ro];
-            ca = acc8_row(f.db3 + (ix >= 0 ? ix : 0) * D3P, j, qs, wsh);
-        }
-        acc[tid] = ta;
-        if (b == 0 && tid < 15 * 8) cacc[tid] = ca;
-        __syncthreads();
-        if (j == 0 && ntl > 0 && r0 + ro < sc.nrows) {
-            const double d = acc8_sum(acc + 8 * ro, false);
-            if (d < bd || (d == bd && r0 + ro < bi)) {
-                bd = d;
-                bi = r0 + ro;
-                const double sq = sqrt(acc8_sum(acc + 8 * ro, true));
-                bw = sq * sq;
-            }
-        }
-        if (b == 0 && j == 0 && tid < 15 * 8) {
-            if (rix[ro] >= 0) {
-                sump[ro] = sqrt(acc8_sum(cacc + 8 * ro, false));
-                const double sq = sqrt(acc8_sum(cacc + 8 * ro, true));
-                sumw[ro] = sq * sq;
-            } else {
-                sump[ro] = INFINITY;
-                sumw[ro] = 0.0;
-            }
-        }
-        __syncthreads();   // acc is refilled by the next tile
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(bd, o), ow = __shfl_xor(bw, o);
-        const long long oi = __shfl_xor(bi, o);
-        if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; bw = ow; }
-    }
-    if (lane == 0) { rd[wv] = bd; ri[wv] = bi; rw[wv] = bw; }
-    __syncthreads();
-    if (wv == 0) {
-    double wd = rd[0], ww = rw[0];
-    long long wi = ri[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-        if (rd[w] < wd || (rd[w] == wd && ri[w] < wi)) { wd = rd[w]; wi = ri[w]; ww = rw[w]; }
-    const long src = c3_decide(f, y, x, lane, wi, ww, sump, sumw, rix, rpos);
-    if (lane < 3) {
-        const double val = f.Ap_lg[src + lane];
-        f.Bp_lg[((long)y * W + x) * 3 + lane] = val;
-        if constexpr (FUSE) {
-            // the decision for the lower neighbour's next query, and this pixel's own
-            ownv[lane] = val;
-            const unsigned long long bits = (unsigned long long)__double_as_longlong(val);
-            unsigned long long *d = nx.dbox + 8 * (long)y + 2 * lane;
-            __hip_atomic_store(d, c3_gran(f.t + 1, (unsigned)bits), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(d + 1, c3_gran(f.t + 1, (unsigned)(bits >> 32)), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    }   // wave 0
-    }   // cur
-    if constexpr (FUSE) {
-        __syncthreads();   // ownv, anydep
-        if (nxt) {
-            if (anydep && tid == 0) {   // the upper neighbour (ticket m - 1) decided (y - 1, x + 3)
-                const unsigned long long *d = nx.dbox + 8 * (long)(y - 1);
-                const unsigned tag = (unsigned)(f.t + 1);
-                const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-                for (;;) {
-                    bool ok = true;
-                    unsigned long long g[6];
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) {
-                        g[c] = __hip_atomic_load(d + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ok = ok && (unsigned)(g[c] >> 32) == tag;
-                    }
-                    if (ok) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c)
-                            nbv[c] = __longlong_as_double(
-                                (long long)(((g[2 * c + 1] & 0xffffffffULL) << 32) | (g[2 * c] & 0xffffffffULL)));
-                        break;
-                    }
-                    if (__builtin_amdgcn_s_memrealtime() - t0 > C3_WAIT_TICKS) {
-                        atomicOr(nx.err, 1u);
-                        nbv[0] = nbv[1] = nbv[2] = 0.0;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-            }
-            __syncthreads();
-            const double v = dep == 1 ? ownv[dch] : dep == 2 ? nbv[dch] : nv;
-            const int mq = y - nx.y_lo_n;
-            if (tid < D3P) nx.q3n[(long)mq * D3P + tid] = tid < D3 ? v : 0.0;
-            r3_query(mq, nx.M_n, tid, v, nx.meta, nx.rot, nx.qnn, nx.nskn, nx.q16n, qds, qred);
-        }
-    }
+#define C3X_BATCH 0
+#define C3X_M nx.M
+#define C3X_YN nx.y_lo_n
+#define C3X_MN nx.M_n
+#include "ia_color3_exact.inc"
+#undef C3X_BATCH
+#undef C3X_M
+#undef C3X_YN
+#undef C3X_MN
+}
+
+// ---- a batch of K identical-shape jobs (ia_synth_levels3_batch) --------------------------
+// One launch of k_query3rb / k_screen3rb / k_exact3b serves K jobs: the block's job is a grid
+// dimension (query, exact: y; screen: z, y being its query group), and job k's pointers and
+// scalars come from entry k of a device job table (one per level, in job 0's workspace).  The
+// wave's scalars stay launch arguments.  Query sets alternate by wave parity on the fused
+// path (set 0 otherwise).  Nothing is shared between jobs.
+constexpr int C3_CTL_ERR = 2;      // the error word's index in ctl
+struct C3Job {
+    Fin3 f;                        // t, y_lo: the launch's; q3: q3[parity]
+    Scr3 sc;                       // qn, nsk: by parity
+    Nx3 nx[2];                     // by parity (M, y_lo_n, M_n: the launch's); read in place
+    const half8 *dbr;
+    float *smin;
+    double *q3[2], *qn[2], *nsk[2];
+    half8 *q16[2];
+};
+__global__ __launch_bounds__(256) void k_query3rb(const C3Job *__restrict__ jobs, int t, int y_lo, int M) {
+    const C3Job &J = jobs[blockIdx.y];
+    const Nx3 &nx = J.nx[0];
+    query3r_body(nx.Bsm, nx.Blg, nx.Bpsm, nx.Bplg, t, y_lo, M, nx.meta, nx.rot, nullptr, J.q3[0], J.qn[0],
+                 J.nsk[0], J.q16[0]);
+}
+__global__ __launch_bounds__(256, 2) void k_screen3rb(const C3Job *__restrict__ jobs, int ntiles, int M,
+                                                      int tpw, int parity) {
+    const C3Job &J = jobs[blockIdx.z];
+    screen3r_body(J.dbr, ntiles, J.q16[parity], M, tpw, J.smin);
+}
+template <bool FUSE>
+__global__ __launch_bounds__(256) void k_exact3b(const C3Job *__restrict__ jobs, int t, int y_lo, int M,
+                                                 int y_lo_n, int M_n) {
+    const C3Job &J = jobs[blockIdx.y];
+    const int b = FUSE ? t & 1 : 0;
+    Fin3 f = J.f;
+    f.t = t;
+    f.y_lo = y_lo;
+    f.q3 = J.q3[b];
+    Scr3 sc = J.sc;
+    sc.qn = J.qn[b];
+    sc.nsk = J.nsk[b];
+    const Nx3 &nx = J.nx[b];
+#define C3X_BATCH 1
+#define C3X_M M
+#define C3X_YN y_lo_n
+#define C3X_MN M_n
+#include "ia_color3_exact.inc"
+#undef C3X_BATCH
+#undef C3X_M
+#undef C3X_YN
+#undef C3X_MN
 }
 
 // The per-pixel tail of the exhaustive fp64 search (IA_COLOR16=0), one 256-thread workgroup
@@ -1341,8 +1218,8 @@ struct Ws3 {
     half8 *q16b;
     unsigned *ctl;           // tickets[2], error word
     unsigned long long *dbox;
+    C3Job *jtab;             // a batch's job table (ia_synth_levels3_batch, job 0's workspace)
 };
-constexpr int C3_CTL_ERR = 2;
 // the fused colour tail (k_exact3<true>: the next wave's query rows from the exact stage's
 // launch; IA_C3_FUSE, default 1) on R16c levels; read per level (Level3::init)
 static inline bool c3_fuse() { return env_int("IA_C3_FUSE", 1) != 0; }
@@ -1363,7 +1240,9 @@ static inline size_t ws3_layout(int H, int W, long nrows, char *base, Ws3 *w) {
     char *nskb = take(Mp * sizeof(double));
     char *ctl = take(256);
     char *dbox = take((size_t)H * 8 * sizeof(unsigned long long));
+    char *jtab = take((size_t)IA_BATCH_MAX * sizeof(C3Job));
     if (w) {
+        w->jtab = reinterpret_cast<C3Job *>(jtab);
         w->q3b = reinterpret_cast<double *>(q3b);
         w->q16b = reinterpret_cast<half8 *>(q16b);
         w->qnb = reinterpret_cast<double *>(qnb);
@@ -1424,10 +1303,70 @@ struct Level3 {
         if (fuse) IA_HIP(hipMemsetAsync(w.dbox, 0, (size_t)H * 8 * sizeof(unsigned long long), st));
         return IA_OK;
     }
+
+    // a batch of K identical-shape jobs (ia_synth_levels3_batch): this run is job 0 and owns
+    // the job table; part holds jobs 1 .. K-1 (their own control words and granules, set up by
+    // their own init)
+    int K = 1;
+    std::vector<Level3> part;
+    C3Job job_entry() const {
+        C3Job J{};
+        J.f = f;
+        J.sc = sc;
+        J.dbr = dbr;
+        J.smin = w.smin;
+        J.q3[0] = w.q3; J.q3[1] = w.q3b;
+        J.qn[0] = w.qn; J.qn[1] = w.qnb;
+        J.nsk[0] = w.nsk; J.nsk[1] = w.nskb;
+        J.q16[0] = w.q16; J.q16[1] = w.q16b;
+        for (int b = 0; b < 2; ++b)   // wave parity b writes the next wave's set b ^ 1
+            J.nx[b] = Nx3{Bsm, Blg, Bpsm, Bplg, 0, 0, 0, H, v.meta, a->rot, J.q3[b ^ 1], J.qn[b ^ 1],
+                          J.nsk[b ^ 1], J.q16[b ^ 1], w.ctl, w.ctl + C3_CTL_ERR, w.dbox};
+        return J;
+    }
+    // args[0..nj): the jobs' levels (validated by ia_synth_levels3_batch); the job table is
+    // staged through `pinned` (kept alive by the caller until the copy has run)
+    int init_batch(const IaSynthArgs *args, int nj, hipStream_t st, C3Job *pinned) {
+        int rc = init(&args[0], st);
+        if (rc || nj == 1) return rc;
+        IA_ARG(rot, "ia_synth_levels3_batch: a batch of K > 1 jobs runs the rotated screen (dbr, rot; IA_COLOR16=1)");
+        K = nj;
+        part.resize(K - 1);
+        for (int k = 1; k < K; ++k) {
+            if ((rc = part[k - 1].init(&args[k], st))) return rc;
+            IA_ARG(part[k - 1].rot && part[k - 1].ntiles == ntiles, "ia_synth_levels3_batch: jobs of different forms");
+        }
+        pinned[0] = job_entry();
+        for (int k = 1; k < K; ++k) pinned[k] = part[k - 1].job_entry();
+        IA_HIP(hipMemcpyAsync(w.jtab, pinned, (size_t)K * sizeof(C3Job), hipMemcpyHostToDevice, st));
+        return IA_OK;
+    }
+    // wave t of a batch: the single job's launches with the job as a grid dimension
+    int wave_batch(int t, int y_lo, int M, hipStream_t st) {
+        const int QT = (M + 31) / 32;
+        int tpw;
+        const dim3 grid = screen3r_grid(ntiles, M, tpw, K);
+        if (fuse) {
+            if (t == 0) k_query3rb<<<dim3(QT * 32, K), 256, 0, st>>>(w.jtab, t, y_lo, M);
+            k_screen3rb<<<grid, 256, 0, st>>>(w.jtab, ntiles, M, tpw, t & 1);
+            int y_lo_n = 0, M_n = 0;
+            if (t + 1 < nw) wave_rows(H, W, t + 1, y_lo_n, M_n);
+            const int R = std::max(M, M_n > 0 ? y_lo_n + M_n - y_lo : 0);
+            k_exact3b<true><<<dim3(R, K), 256, 0, st>>>(w.jtab, t, y_lo, M, y_lo_n, M_n);
+        } else {
+            k_query3rb<<<dim3(QT * 32, K), 256, 0, st>>>(w.jtab, t, y_lo, M);
+            k_screen3rb<<<grid, 256, 0, st>>>(w.jtab, ntiles, M, tpw, 0);
+            k_exact3b<false><<<dim3(M, K), 256, 0, st>>>(w.jtab, t, y_lo, M, 0, 0);
+        }
+        IA_LAUNCH_CHECK("ia_synth_levels3_batch wave");
+        return IA_OK;
+    }
+
     int wave(int t, hipStream_t st) {
         int y_lo, M;
         wave_rows(H, W, t, y_lo, M);
         if (M <= 0) return IA_OK;
+        if (K > 1) return wave_batch(t, y_lo, M, st);
         f.t = t;
         f.y_lo = y_lo;
         if (fuse) {
@@ -1632,24 +1571,69 @@ int ia_synth_level3(const IaSynthArgs *a, void *stream) {
 /* n consecutive 3-channel levels through the level pipeline of ia_synth_levels (ia_pipe.h),
  * every level enqueued whole, coarse to fine (order 1): a level's waits name events already
  * recorded.  Finest-first as the luminance path (IA_PIPE_ORDER 0) is a speed change yet to be
- * measured here. */
-int ia_synth_levels3(const IaSynthArgs *levels, int n, void *stream) {
-    IA_ARG(levels && n >= 1 && n <= 64, "ia_synth_levels3: bad level count");
+ * measured here.
+ * K > 1 (ia_synth_levels3_batch): levels[j * K + k] is level j of job k; every level's run is
+ * job 0's Level3 with the other jobs as its parts and one job table, and every wave is one
+ * set of launches for the K jobs. */
+static int synth_levels3(const IaSynthArgs *levels, int n, int K, void *stream) {
+    const std::string who = K > 1 ? "ia_synth_levels3_batch" : "ia_synth_levels3";
+    IA_ARG(levels && n >= 1 && n <= 64, who + ": bad level count");
     for (int j = 1; j < n; ++j)
-        IA_ARG(levels[j].Bp_sm == levels[j - 1].Bp_lg && levels[j].B_hs == levels[j - 1].H &&
-                   levels[j].B_ws == levels[j - 1].W,
-               "ia_synth_levels3: levels must be consecutive (level j's coarse B' = level j-1's B')");
+        for (int k = 0; k < K; ++k) {
+            const IaSynthArgs &c = levels[(size_t)(j - 1) * K + k], &l = levels[(size_t)j * K + k];
+            IA_ARG(l.Bp_sm == c.Bp_lg && l.B_hs == c.H && l.B_ws == c.W,
+                   who + ": levels must be consecutive (level j's coarse B' = level j-1's B')");
+        }
+    // a batch: every job of a level in the same shapes and forms (checked before anything is
+    // enqueued; the message names the field)
+    if (K > 1) {
+        IA_ARG(g_color16.load(std::memory_order_relaxed) != 0,
+               who + ": K > 1 needs the screened matcher (IA_COLOR16=1)");
+        for (int j = 0; j < n; ++j) {
+            const IaSynthArgs &a = levels[(size_t)j * K];
+            for (int k = 0; k < K; ++k) {
+                const IaSynthArgs &b = levels[(size_t)j * K + k];
+#define IA_SAME(field) IA_ARG(b.field == a.field, who + ": the jobs of a batch differ in " #field)
+                IA_SAME(H); IA_SAME(W); IA_SAME(B_hs); IA_SAME(B_ws);
+                IA_SAME(src.Ah); IA_SAME(src.Aw); IA_SAME(src.A_hs); IA_SAME(src.A_ws); IA_SAME(src.nAp);
+                IA_SAME(nrows);
+#undef IA_SAME
+                IA_ARG(!b.dbg_px == !a.dbg_px && !b.dbg_dist == !a.dbg_dist,
+                       who + ": the jobs of a batch differ in having debug outputs (dbg_px, dbg_dist)");
+                IA_ARG(!b.dbr == !a.dbr && !b.rot == !a.rot,
+                       who + ": the jobs of a batch differ in having a rotated DB (dbr, rot)");
+                IA_ARG(!b.comm, who + ": a batch takes no comm");
+                IA_ARG(!b.lsh, who + ": a batch takes no lsh");
+                IA_ARG(b.row0 == 0 && b.nrows == (long)b.src.nAp * b.src.Ah * b.src.Aw,
+                       who + ": a batch takes no partial row range (row0, nrows)");
+                IA_ARG(b.dbr && b.rot,
+                       who + ": K > 1 needs the rotated DB (dbr, rot): the batch form exists for the R16c screen");
+            }
+        }
+    }
     hipStream_t st = S(stream);
     int rc = g_pipe.begin(n, st);
     if (rc) return rc;
+    // the job tables go through this thread's pinned staging buffer (ia_pipe.h)
+    C3Job *pinned = nullptr;
+    if (K > 1) IA_HIP(g_pipe.staging((size_t)n * K * sizeof(C3Job), reinterpret_cast<void **>(&pinned)));
     std::vector<Level3> run(n);
     std::vector<PipeLevel> pl(n);
     for (int j = 0; j < n; ++j) {
-        if ((rc = g_pipe.level_begin(j)) || (rc = run[j].init(&levels[j], g_pipe.stream(j)))) return rc;
+        if ((rc = g_pipe.level_begin(j)) ||
+            (rc = run[j].init_batch(&levels[(size_t)j * K], K, g_pipe.stream(j), pinned ? pinned + (size_t)j * K : nullptr)))
+            return rc;
         // (the fused tail's launch of wave t also builds wave t + 1's query rows)
         pl[j] = PipeLevel{run[j].H, run[j].W, run[j].fuse, false};
     }
     return pipe_execute(run, pl, 1, 0, st);
+}
+
+int ia_synth_levels3(const IaSynthArgs *levels, int n, void *stream) { return synth_levels3(levels, n, 1, stream); }
+
+int ia_synth_levels3_batch(const IaSynthArgs *levels, int n, int K, void *stream) {
+    IA_ARG(K >= 1 && K <= IA_BATCH_MAX, "ia_synth_levels3_batch: K out of range (1 .. 128)");
+    return synth_levels3(levels, n, K, stream);
 }
 
 int ia_diag_screen3(const void *db3, long nrows, const double *q165, int M, double *e, double *eps,

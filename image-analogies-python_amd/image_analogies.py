@@ -214,6 +214,53 @@ def _src_level3(A_sm, A_lg, Ap_sm, Ap_lg):
     return src
 
 
+def _db3_level(A_pyr, Ap_pyr_list, level):
+    """One level's 3-channel database (ia_db3_build): (A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3)."""
+    lib = _ia.lib()
+    A_sm, A_lg = A_pyr[level - 1].contiguous(), A_pyr[level].contiguous()
+    Ap_sm = torch.stack([p[level - 1] for p in Ap_pyr_list]).contiguous()
+    Ap_lg = torch.stack([p[level] for p in Ap_pyr_list]).contiguous()
+    src = _src_level3(A_sm, A_lg, Ap_sm, Ap_lg)
+    N = src.nAp * src.Ah * src.Aw
+    db3 = torch.empty(lib.ia_db3_bytes(N) // 8, dtype=torch.float64, device=A_lg.device)
+    _ia.check(lib.ia_db3_build(ctypes.byref(src), 0, N, _ia.ptr(db3), _ia.stream()), 'ia_db3_build')
+    return A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3
+
+
+def _level3_args(built, rot, dbr, B_pyr, Bp_pyr, level, max_levels, k, weights, debug):
+    """IaSynthArgs of one 3-channel level over _db3_level's database (rot, dbr: its rotated
+    form or None): (args, (s, im, debug record or None), buffers to keep alive)."""
+    lib = _ia.lib()
+    A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3 = built
+    dev = A_lg.device
+    B_sm, B_lg = B_pyr[level - 1].contiguous(), B_pyr[level].contiguous()
+    Bp_sm, Bp_lg = Bp_pyr[level - 1], Bp_pyr[level]
+    assert Bp_lg.is_contiguous() and Bp_sm.is_contiguous()
+    H, W = B_lg.shape[:2]
+    s = torch.empty((H * W, 2), dtype=torch.int32, device=dev)
+    im = torch.empty(H * W, dtype=torch.int32, device=dev)
+    dbg = None
+    if debug:
+        dbg = (torch.zeros((H * W, 7), dtype=torch.int32, device=dev),
+               torch.zeros((H * W, 2), dtype=torch.float64, device=dev))
+    ws = _ia.workspace(lib.ia_synth3_workspace_bytes(H, W, N))
+    a = _ia.IaSynthArgs()
+    a.src = src
+    a.db, a.row0, a.nrows, a.N_total = _ia.ptr(db3).value, 0, N, N
+    a.B_sm, a.B_lg = _ia.ptr(B_sm).value, _ia.ptr(B_lg).value
+    a.B_hs, a.B_ws = B_sm.shape[:2]
+    a.H, a.W = H, W
+    a.Bp_sm, a.Bp_lg = _ia.ptr(Bp_sm).value, _ia.ptr(Bp_lg).value
+    a.weights = _ia.ptr(weights).value
+    a.kappa_factor = kappa_factor(level, max_levels, k)
+    a.s, a.im, a.workspace = _ia.ptr(s).value, _ia.ptr(im).value, _ia.ptr(ws).value
+    if rot is not None:
+        a.dbr, a.rot = _ia.ptr(dbr).value, _ia.ptr(rot).value
+    if dbg is not None:
+        a.dbg_px, a.dbg_dist = _ia.ptr(dbg[0]).value, _ia.ptr(dbg[1]).value
+    return a, (s, im, dbg), (B_sm, B_lg, ws)
+
+
 def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, levels=None,
                     debug=False, pipeline=None):
     """3-channel synthesis (num_ch = 3: convert=False on colour images, 165-dim rows): per
@@ -233,16 +280,7 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
         pipeline = pipeline_default()
     out, args, keep, done = {}, [], [], []
     todo = [l for l in range(1, max_levels) if levels is None or l in levels]
-    built = {}
-    for level in todo:
-        A_sm, A_lg = A_pyr[level - 1].contiguous(), A_pyr[level].contiguous()
-        Ap_sm = torch.stack([p[level - 1] for p in Ap_pyr_list]).contiguous()
-        Ap_lg = torch.stack([p[level] for p in Ap_pyr_list]).contiguous()
-        src = _src_level3(A_sm, A_lg, Ap_sm, Ap_lg)
-        N = src.nAp * src.Ah * src.Aw
-        db3 = torch.empty(lib.ia_db3_bytes(N) // 8, dtype=torch.float64, device=A_lg.device)
-        _ia.check(lib.ia_db3_build(ctypes.byref(src), 0, N, _ia.ptr(db3), st), 'ia_db3_build')
-        built[level] = (A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3)
+    built = {level: _db3_level(A_pyr, Ap_pyr_list, level) for level in todo}
     # the rotated split screen (R16c), bit-identical results: one rotation for every level,
     # the principal directions of the finest level's rows (IA_ROT3_SHARED, default 1: one
     # device sync and one 165 x 165 eigh per call instead of one per level; the coarser
@@ -254,37 +292,13 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
         shared = algorithms.rot3_rotation(db3f, Nf)
     for level in todo:
         A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3 = built[level]
-        dev = A_lg.device
         rot = dbr = None
         if shared is not None:
             rot, dbr = shared, algorithms.rot3_apply(db3, N, shared)
         elif _ia.db_rot_enabled():
             rot, dbr = algorithms.rot3_build(db3, N)
-        B_sm, B_lg = B_pyr[level - 1].contiguous(), B_pyr[level].contiguous()
-        Bp_sm, Bp_lg = Bp_pyr[level - 1], Bp_pyr[level]
-        assert Bp_lg.is_contiguous() and Bp_sm.is_contiguous()
-        H, W = B_lg.shape[:2]
-        s = torch.empty((H * W, 2), dtype=torch.int32, device=dev)
-        im = torch.empty(H * W, dtype=torch.int32, device=dev)
-        dbg = None
-        if debug:
-            dbg = (torch.zeros((H * W, 7), dtype=torch.int32, device=dev),
-                   torch.zeros((H * W, 2), dtype=torch.float64, device=dev))
-        ws = _ia.workspace(lib.ia_synth3_workspace_bytes(H, W, N))
-        a = _ia.IaSynthArgs()
-        a.src = src
-        a.db, a.row0, a.nrows, a.N_total = _ia.ptr(db3).value, 0, N, N
-        a.B_sm, a.B_lg = _ia.ptr(B_sm).value, _ia.ptr(B_lg).value
-        a.B_hs, a.B_ws = B_sm.shape[:2]
-        a.H, a.W = H, W
-        a.Bp_sm, a.Bp_lg = _ia.ptr(Bp_sm).value, _ia.ptr(Bp_lg).value
-        a.weights = _ia.ptr(weights).value
-        a.kappa_factor = kappa_factor(level, max_levels, k)
-        a.s, a.im, a.workspace = _ia.ptr(s).value, _ia.ptr(im).value, _ia.ptr(ws).value
-        if rot is not None:
-            a.dbr, a.rot = _ia.ptr(dbr).value, _ia.ptr(rot).value
-        if dbg is not None:
-            a.dbg_px, a.dbg_dist = _ia.ptr(dbg[0]).value, _ia.ptr(dbg[1]).value
+        a, (s, im, dbg), (B_sm, B_lg, ws) = _level3_args(built[level], rot, dbr, B_pyr, Bp_pyr, level,
+                                                         max_levels, k, weights, debug)
         done.append((a, (A_sm, A_lg, Ap_sm, Ap_lg, B_sm, B_lg, db3, ws, rot, dbr)))
         if not pipeline:
             _ia.check(lib.ia_synth_level3(ctypes.byref(a), st), 'ia_synth_level3')
@@ -305,6 +319,60 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
         arr = (_ia.IaSynthArgs * len(done))(*[x[0] for x in done])
         _ia.check(lib.ia_synth3_status(arr, len(done), st), 'ia_synth3_status')
     return out
+
+
+def rot3_batch_shared():
+    """One rotation per colour batch (job 0's finest level) instead of one per job
+    (IA_ROT3_BATCH_SHARED, default 1: DESIGN.md §3c has the measurement)."""
+    return os.environ.get('IA_ROT3_BATCH_SHARED', '1') != '0'
+
+
+def synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=False, check=True, rot_shared=None):
+    """K 3-channel analogies of identical shapes in ONE set of launches per wave
+    (ia_synth_levels3_batch: k_screen3r and the fused k_exact3<true> with the job as a grid
+    dimension).  Per job and level its own database (ia_db3_build), rotated database
+    (ia_db3_build_rot) and workspace; the rotation is one per batch (the principal directions
+    of job 0's finest level; rot_shared / IA_ROT3_BATCH_SHARED, default 1) or one per job (its
+    own finest level, as IA_ROT3_SHARED within a job): any orthonormal basis keeps the matcher
+    exact, so the results are those of synthesize3_dev per job either way.  The batch form
+    exists for the rotated screen only: with IA_DB_ROT=0 or the exhaustive search
+    (IA_COLOR16=0) the jobs run one after the other through synthesize3_dev.  jobs, ks, the
+    return value: as synthesize_batch_dev."""
+    lib = _ia.lib()
+    st = _ia.stream()
+    K = len(jobs)
+    weights = weights if torch.is_tensor(weights) else _ia.to_dev(weights)
+    if K == 1 or not _ia.db_rot_enabled() or lib.ia_diag_set_color16(-1) == 0:
+        return [synthesize3_dev(A_pyr, Ap_list, B_pyr, Bp_pyr, max_levels, kj, weights, debug=debug)
+                for (A_pyr, Ap_list, B_pyr, Bp_pyr), kj in zip(jobs, ks)]
+    if rot_shared is None:
+        rot_shared = rot3_batch_shared()
+    levels = list(range(1, max_levels))
+    if not levels:
+        return [{} for _ in jobs]
+    built = [{level: _db3_level(A_pyr, Ap_list, level) for level in levels}
+             for A_pyr, Ap_list, _, _ in jobs]
+    rots = []
+    for q in range(K if not rot_shared else 1):
+        Nf, db3f = built[q][levels[-1]][5:7]
+        rots.append(algorithms.rot3_rotation(db3f, Nf))
+    args, keep, res = [], [], [{} for _ in jobs]     # level-major: args[j * K + job]
+    for level in levels:
+        for q, ((_, _, B_pyr, Bp_pyr), kj) in enumerate(zip(jobs, ks)):
+            N, db3 = built[q][level][5:7]
+            rot = rots[q if not rot_shared else 0]
+            dbr = algorithms.rot3_apply(db3, N, rot)
+            a, (s, im, dbg), bufs = _level3_args(built[q][level], rot, dbr, B_pyr, Bp_pyr, level,
+                                                 max_levels, kj, weights, debug)
+            args.append(a)
+            keep.append((bufs, dbr))
+            res[q][level] = (s, im) if dbg is None else (s, im, dbg)
+    arr = (_ia.IaSynthArgs * len(args))(*args)
+    _ia.check(lib.ia_synth_levels3_batch(arr, len(levels), K, st), 'ia_synth_levels3_batch')
+    if check:
+        _ia.check(lib.ia_synth3_status(arr, len(args), st), 'ia_synth3_status')
+    del keep, built
+    return res
 
 
 def synthesize_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights,
@@ -407,15 +475,19 @@ def synthesize_batch_dev(jobs, max_levels, k, weights, prof=False, debug=False, 
     pyramids (Bp_pyr updated in place); k: one kappa or one per job.  Every level of every
     job is synthesised exactly as synthesize_dev would (exact matcher, one GPU); each wave's
     screen and fused kernel serve all K jobs at once (ia_synth_levels_batch), so the batch
-    costs about one job's per-wave launch latency.  Returns one {level: (s, im[, debug])}
-    dict per job."""
+    costs about one job's per-wave launch latency.  Jobs of 3-channel pyramids (all of them:
+    a mix raises ValueError) go to synthesize3_batch_dev.  Returns one {level: (s, im[,
+    debug])} dict per job."""
     K = len(jobs)
     if K == 0:
         return []
     ks = list(k) if isinstance(k, (list, tuple)) else [k] * K
+    colour = [j[2][-1].dim() == 3 for j in jobs]
+    if any(colour):
+        if not all(colour):
+            raise ValueError('synthesize_batch_dev: a batch is all 3-channel or all luminance jobs')
+        return synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=debug, check=check)
     w = weights if torch.is_tensor(weights) else _ia.to_dev(weights)
-    if any(j[2][-1].dim() == 3 for j in jobs):
-        raise NotImplementedError('batches run 1-channel (luminance) matching')
     levels = list(range(1, max_levels))
     calls = []          # level-major: calls[j * K + job]
     # K databases per launch: fewer, longer chunks per database (the screen's workgroups
@@ -680,7 +752,6 @@ def image_analogies_main(A_fname, Ap_fname_list, B_fname, out_path, c, debug=Fal
     exchanges the caller made (then pass rank and nranks).  Every rank ends with the same
     B' (the exchange is deterministic); only rank 0 writes the output files and prints.
     To spread independent runs over GPUs instead (the multi_script loop) use multi_main."""
-    import matplotlib.pyplot as plt
     r0, w0 = dist_world()
     rank = r0 if rank is None else rank
     nranks = (w0 if comm is not None else 1) if nranks is None else nranks
@@ -721,6 +792,17 @@ def image_analogies_main(A_fname, Ap_fname_list, B_fname, out_path, c, debug=Fal
     say('Synthesis time: %f' % (time.time() - start_time))
     if not lead:
         return [p.cpu().numpy() for p in Bp_pyr]
+    write_outputs(res, Bp_pyr, color_pyr_list, c, out_path, debug, outputs)
+    print('Total time: %f' % (time.time() - begin_time))
+    return [p.cpu().numpy() for p in Bp_pyr]
+
+
+def write_outputs(res, Bp_pyr, color_pyr_list, c, out_path, debug=False, outputs=None):
+    """What image_analogies_main does with a finished synthesis (image_analogies.py:216-258):
+    per level the colour image (color_output) saved as level_<l>_color.jpg and as the run's
+    <name>.jpg, with debug the debug structures (save_debug), and the entries of `outputs`.
+    res: synthesize_dev's (or one job of synthesize_batch_dev's) return value."""
+    import matplotlib.pyplot as plt
     for level in range(1, c.max_levels):
         s, im = res[level][0], res[level][1]
         color_im_out = color_output(level, Bp_pyr[level], s, im, color_pyr_list, c)
@@ -734,23 +816,81 @@ def image_analogies_main(A_fname, Ap_fname_list, B_fname, out_path, c, debug=Fal
                 outputs[level]['debug'] = rec
         plt.imsave(out_path + 'level_%d_color.jpg' % level, color_im_out)
         plt.imsave(out_path + out_path.split('/')[-2] + '.jpg', color_im_out)
-    print('Total time: %f' % (time.time() - begin_time))
-    return [p.cpu().numpy() for p in Bp_pyr]
 
 
-def multi_main(runs, c, debug=False, rank=None, world=None):
+def _run_key(c, A_pyr, Ap_pyr_list, B_pyr):
+    """What the runs of one batch agree on (multi_main): channel count, levels, every pyramid
+    shape, the number of A' images, the exact matcher."""
+    shapes = tuple(tuple(p.shape) for pyr in (A_pyr, B_pyr) for p in pyr)
+    return (c.num_ch, c.max_levels, shapes, len(Ap_pyr_list), algorithms.lsh_params(c) is None)
+
+
+def _multi_batch(group, c, debug):
+    """multi_main's batched path for the runs `group` ([(j, run)], at most `batch` of them):
+    each run is set up under its own copy of the config (its overrides apply to it alone);
+    runs that agree on _run_key are synthesised by one synthesize_batch_dev call, each with
+    its own kappa, every other run alone; then each run's outputs as image_analogies_main
+    writes them.  Returns {j: B' pyramid}."""
+    import types
+    ready = []
+    for j, run in group:
+        A_fname, Ap_fname_list, B_fname, out_path = run[:4]
+        cj = types.SimpleNamespace(**{f: v for f, v in vars(c).items() if not f.startswith('__')})
+        for key, val in (run[4] if len(run) > 4 else {}).items():
+            setattr(cj, key, val)
+        if not os.path.exists(out_path):
+            os.makedirs(out_path)
+        pyrs = setup_dev(_read(A_fname), [_read(f) for f in Ap_fname_list], _read(B_fname), cj)
+        save_metadata(out_path, ['A_fname', 'Ap_fname_list', 'B_fname', 'c.convert', 'c.remap_lum',
+                                 'c.init_rand', 'c.AB_weight', 'c.k'],
+                      [A_fname, Ap_fname_list, B_fname, cj.convert, cj.remap_lum, cj.init_rand,
+                       cj.AB_weight, cj.k])
+        ready.append((j, out_path, cj, pyrs, _run_key(cj, pyrs[0], pyrs[1], pyrs[2])))
+    results = {}
+    for key in dict.fromkeys(r[4] for r in ready):          # (first-seen order)
+        same = [r for r in ready if r[4] == key]
+        c0 = same[0][2]
+        weights = _ia.to_dev(c0.weights)
+        if len(same) > 1 and key[4]:
+            res = synthesize_batch_dev([r[3][:4] for r in same], c0.max_levels, [r[2].k for r in same],
+                                       weights, debug=debug)
+        else:
+            res = [synthesize_dev(*r[3][:4], r[2].max_levels, r[2].k, weights,
+                                  lsh=algorithms.lsh_params(r[2]), debug=debug) for r in same]
+        results.update((r[0], x) for r, x in zip(same, res))
+    torch.cuda.synchronize()
+    out = {}
+    for j, out_path, cj, pyrs, _ in ready:
+        write_outputs(results[j], pyrs[3], pyrs[4], cj, out_path, debug)
+        out[j] = [p.cpu().numpy() for p in pyrs[3]]
+    return out
+
+
+def multi_main(runs, c, debug=False, rank=None, world=None, batch=0):
     """The reference's batch scripts (multi_script.py:13-32, multi_script_2.py:31-40: a
     serial loop of image_analogies_main calls, each with its own files and kappa) spread over
     GPUs, one process per GPU: this rank runs runs[j] for j in rank_jobs(len(runs), rank,
     world) (rank / world default to the initialised torch.distributed group's; (0, 1)
     without one), each on its own GPU alone.  runs: (A_fname, Ap_fname_list, B_fname,
     out_path[, overrides]) tuples; overrides is a dict of config fields set on `c` before
-    the run (multi_script.py:31 sets c.k so).  Returns {j: B' pyramid} of this rank's runs."""
+    the run (multi_script.py:31 sets c.k so).  batch = K > 1: this rank's runs are set up in
+    order in groups of at most K, and the runs of a group that agree on the channel count,
+    max_levels, every pyramid shape, the number of A' images and the exact matcher are
+    synthesised by ONE synthesize_batch_dev call (luminance or 3-channel), each with its own
+    kappa; every other run goes alone.  A batched run writes the same files with the same
+    bytes as an unbatched one; on this path a run's overrides apply to that run only (each run
+    takes a copy of `c`), while the unbatched loop sets them on `c` itself as before.
+    Returns {j: B' pyramid} of this rank's runs."""
     r0, w0 = dist_world()
     rank = r0 if rank is None else rank
     world = w0 if world is None else world
     out = {}
-    for j in rank_jobs(len(runs), rank, world):
+    mine = rank_jobs(len(runs), rank, world)
+    if batch and batch > 1:
+        for g0 in range(0, len(mine), batch):
+            out.update(_multi_batch([(j, runs[j]) for j in mine[g0:g0 + batch]], c, debug))
+        return out
+    for j in mine:
         A_fname, Ap_fname_list, B_fname, out_path = runs[j][:4]
         for key, val in (runs[j][4] if len(runs[j]) > 4 else {}).items():
             setattr(c, key, val)

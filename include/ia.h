@@ -322,6 +322,18 @@ int ia_synth_level3(const IaSynthArgs *a, void *stream);
  * IA_E_SCHED if a wait for a neighbouring pixel's decision timed out in the fused colour tail */
 int ia_synth3_status(const IaSynthArgs *levels, int n, void *stream);
 int ia_synth_levels3(const IaSynthArgs *levels, int n, void *stream);
+/* K independent 3-channel jobs of identical shapes (the multi_script batch with convert=False,
+ * multi_script.py:5), n consecutive levels each: levels[j * K + k] is level j of job k, as in
+ * ia_synth_levels_batch.  Every job keeps its own DB, rotated DB (dbr / rot: its own or one
+ * shared rotation), workspace and outputs; each wave of each level is ONE k_screen3r launch
+ * and ONE k_exact3 launch for all K jobs (the job is a grid dimension, per-job pointers come
+ * from a device job table), through the same level pipeline as ia_synth_levels3.  Results
+ * equal K separate ia_synth_levels3 calls; ia_synth3_status takes all n * K args.
+ * 1 <= K <= 128; K = 1 is ia_synth_levels3.  IA_E_ARG (nothing launched) when the jobs differ
+ * in a shape (H, W, B_hs, B_ws, src.Ah / Aw / A_hs / A_ws / nAp, nrows), in having debug
+ * outputs or dbr / rot, when a job has a comm, an lsh or a partial row range, and when K > 1
+ * without the rotated DB (the batch form exists for the R16c screen only). */
+int ia_synth_levels3_batch(const IaSynthArgs *levels, int n, int K, void *stream);
 /* the rotated split screen for 3-channel rows (R16c): after ia_db3_build, the
  * caller takes the principal directions V of the level's centred rows (165 x 165, columns by
  * decreasing variance; any V orthonormal to fp64 precision keeps the matcher exact: checked,

@@ -3,7 +3,11 @@ config.py:29-42 num_ch = 3, 165-dim rows, algorithms.py:11-47) on one GPU, next 
 luminance path on the same images (their Y channel): B' pixels per second of whole
 syntheses (device pyramids, B' reset, every level), inputs resident in HBM.
 
-usage: python tools/colour_bench.py [H W] [steps]      (default 180 117 (c1 size), 3 steps)
+usage: python tools/colour_bench.py [H W] [steps] [jobs]   (default 180 117 (c1 size), 3 steps, 1 job)
+       jobs = K > 1: a batch of K colour jobs of that size with distinct seeds in one
+       synthesize_batch_dev call (ia_synth_levels3_batch): ms per step and per job, every
+       step's time, the candidate tiles per query, under one rotation per batch and one per
+       job (IA_ROT3_BATCH_SHARED both ways)
        COLOUR_PIPE=0: the colour levels one at a time (default: pipelined, ia_synth_levels3)
        COLOUR_ONLY=1: the 3-channel run alone (kernel traces of it)
 Also reports the colour exact stage's candidate tiles per query (ia_diag_color16_stats) and a
@@ -24,9 +28,65 @@ import torch  # noqa: E402
 ip, cfg, ia = bench.ip, bench.cfg, bench.ia
 
 
+def batch_main(H, W, steps, K):
+    """K colour jobs of H x W with distinct seeds as one batch."""
+    import ctypes
+    import _ia
+    from scipy.ndimage import gaussian_filter
+    dev = 'cuda:0'
+    w = torch.as_tensor(cfg.compute_weights(3, 5, 12, 3)).to(dev)
+    nB = ip.num_layers(H, W, cfg.n_sm, None)
+    L = nB + 1
+    shapes = [(H, W, 3)]
+    for _ in range(nB):
+        shapes.append(((shapes[-1][0] + 1) // 2, (shapes[-1][1] + 1) // 2, 3))
+    shapes.reverse()
+    pixels = sum(s[0] * s[1] for s in shapes[1:L])
+    srcs = []
+    for q in range(K):
+        A = np.dstack([bench.smooth_noise(7 + 17 * c + 101 * q, (H, W)) for c in range(3)])
+        Ap = np.dstack([gaussian_filter(A[..., c], 1.5) for c in range(3)])
+        B = np.dstack([bench.smooth_noise(8 + 17 * c + 101 * q, (H, W)) for c in range(3)])
+        init = [torch.as_tensor(x).to(dev) for x in ip.initialize_Bp([np.empty(s) for s in shapes], True, 9 + q)]
+        srcs.append(tuple(torch.as_tensor(x).to(dev) for x in (A, Ap, B)) + (init, [x.clone() for x in init]))
+    out = {'size': [H, W], 'jobs': K, 'steps': steps, 'pixels_per_job': pixels}
+    st = (ctypes.c_ulonglong * 2)()
+    for name, shared in (('rotation_per_batch', True), ('rotation_per_job', False)):
+        def step():
+            jobs = []
+            for a, ap, b, init, Bp in srcs:
+                for d, s in zip(Bp, init):
+                    d.copy_(s)
+                jobs.append((ip.gaussian_pyramid_dev(a, cfg.n_sm), [ip.gaussian_pyramid_dev(ap, cfg.n_sm)],
+                             ip.gaussian_pyramid_dev(b, cfg.n_sm), Bp))
+            ia.synthesize3_batch_dev(jobs, L, [0.5] * K, w, rot_shared=shared)
+
+        _ia.check(_ia.lib().ia_diag_color16_stats(st), 'stats')   # (reads and clears)
+        step()
+        torch.cuda.synchronize()
+        _ia.check(_ia.lib().ia_diag_color16_stats(st), 'stats')
+        cand = (st[0] / (pixels * K), int(st[1]))
+        step()                                                   # (second warm-up)
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) * 1e3)
+        med = float(np.median(times))
+        out[name] = {'ms_per_step': med, 'ms_per_job': med / K, 'ms_steps': [round(t, 3) for t in times],
+                     'px_per_s': pixels * K / (med * 1e-3), 'candidate_tiles_per_query': cand[0],
+                     'full_scans': cand[1],
+                     'bp_checksum': float(sum(float(x.sum()) for s in srcs for x in s[4][1:L]))}
+    print(json.dumps(out))
+
+
 def main():
     H, W = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (180, 117)
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    if len(sys.argv) > 4 and int(sys.argv[4]) > 1:
+        return batch_main(H, W, steps, int(sys.argv[4]))
     from scipy.ndimage import gaussian_filter
     dev = 'cuda:0'
     A = np.dstack([bench.smooth_noise(7 + 17 * c, (H, W)) for c in range(3)])
