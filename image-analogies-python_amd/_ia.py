@@ -55,7 +55,8 @@ class IaSynthArgs(ctypes.Structure):
                 ('kappa_factor', ctypes.c_double), ('s', _dp), ('im', _dp),
                 ('workspace', _dp), ('comm', _dp), ('lsh', ctypes.POINTER(IaLsh)),
                 ('flags', ctypes.c_int), ('tag', ctypes.c_int), ('dbg_px', _dp),
-                ('dbg_dist', _dp), ('dbi', _dp), ('dbr', _dp), ('rot', _dp), ('dbk', _dp)]
+                ('dbg_dist', _dp), ('dbi', _dp), ('dbr', _dp), ('rot', _dp), ('dbk', _dp),
+                ('rot_axes', ctypes.c_int)]
 
 
 class IaShardDb(ctypes.Structure):
@@ -92,6 +93,7 @@ _SIGS = {
     'ia_db_rot_applies': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long]),
     'ia_db_rot_bytes': (ctypes.c_size_t, [ctypes.c_long]),
     'ia_db_rot_components': (ctypes.c_int, []),
+    'ia_db_rotk_span': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     'ia_screen_resources': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     'ia_fused_resources': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     'ia_level_resources': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.POINTER(ctypes.c_int)]),
@@ -201,6 +203,9 @@ _SIGS = {
                                          _dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
     'ia_diag_set_compact_min_rows': (ctypes.c_long, [ctypes.c_long]),
     'ia_diag_wave_compact': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    'ia_diag_wave_compact_col': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    'ia_diag_set_compact_col': (ctypes.c_int, [ctypes.c_int]),
+    'ia_diag_level_compact_col': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.c_int]),
     'ia_diag_compact_waves': (ctypes.c_long, []),
     'ia_diag_set_xsplit_min_rows': (ctypes.c_long, [ctypes.c_long]),
     'ia_diag_xsplit_grid': (ctypes.c_int, [ctypes.c_int, ctypes.c_long, ctypes.c_int]),

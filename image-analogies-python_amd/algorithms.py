@@ -140,16 +140,25 @@ class LevelIndex:
         C = cov[:56 * 56].view(56, 56)[:55, :55].cpu().numpy()
         w, V = _eigh(C)
         V = V[:, ::-1]                       # components by decreasing variance
+        self.rot_var = w[::-1].copy()
+        self.rot_axes = 0
+        # where the level takes the compact DB: the own-row axes inside its kept span, so that
+        # the column-0 waves can take the compact screen too (compact_axes_basis).  Only with
+        # that switch on: the axes cost the clean waves two principal components (c4: +10
+        # ms/step with the column waves off, profiles/compact_col_ab.txt)
+        rotk = lib.ia_db_rotk_applies(ctypes.byref(self.src), self.row0, self.nrows)
+        if rotk and lib.ia_diag_set_compact_col(-1):
+            kept, axes = rotk_span()
+            V, self.rot_var, self.rot_axes = compact_axes_basis(C, V, self.rot_var, kept, axes)
         R = np.zeros(_ia.R16_ROT_FLOATS, dtype=np.float32)
         R[:56 * 56].reshape(56, 56)[:55, :55] = V.astype(np.float32)
-        self.rot_var = w[::-1].copy()
         self.rot = torch.as_tensor(R).to(dev)
         self.dbr = torch.empty(lib.ia_db_rot_bytes(self.nrows), dtype=torch.uint8, device=dev)
         _ia.check(lib.ia_db_build_rot(ctypes.byref(self.src), self.row0, self.nrows,
                                       _ia.ptr(self.center), _ia.ptr(self.rot), _ia.ptr(self.amax),
                                       _ia.ptr(self.dbr), st), 'ia_db_build_rot')
         # the compact rotated DB (24 leading components, 64 B per row) where the level takes it
-        if lib.ia_db_rotk_applies(ctypes.byref(self.src), self.row0, self.nrows):
+        if rotk:
             self.dbk = torch.empty(lib.ia_db_rotk_bytes(self.nrows), dtype=torch.uint8, device=dev)
             _ia.check(lib.ia_db_build_rotk(ctypes.byref(self.src), self.row0, self.nrows,
                                            _ia.ptr(self.center), _ia.ptr(self.rot), _ia.ptr(self.amax),
@@ -229,6 +238,63 @@ def _eigh(C):
         return np.linalg.eigh(C)
     with threadpool_limits(1):
         return np.linalg.eigh(C)
+
+
+def rotk_span():
+    """(kept, axes) of the compact screen (ia_db_rotk_span): the components its DB carries and
+    the feature axes a compact level's basis holds among them."""
+    kept = ctypes.c_int(0)
+    axes = (ctypes.c_int * 8)()
+    n = _ia.lib().ia_db_rotk_span(ctypes.byref(kept), axes, 8)
+    return kept.value, [int(a) for a in axes[:n]]
+
+
+AXIS_IN_SPAN = 1e-3   # an axis whose residual against the kept columns is shorter is left out
+
+
+def compact_axes_basis(C, V, var, kept, axes):
+    """The basis of a level that takes the compact DB (DESIGN.md §4d "Which waves").  V: the
+    principal directions of the covariance C as columns by decreasing variance `var`.  Returns
+    (V', var', n): V' keeps columns 0 .. kept - n - 1 of V, holds in columns kept - n .. kept - 1
+    the residuals of the unit vectors e_k (k in axes, in order) against them, orthonormalised
+    (two passes of modified Gram-Schmidt, fp64), and in columns kept .. the principal directions
+    of C on the orthogonal complement of those `kept` columns, by decreasing variance; var' =
+    diag(V'^T C V').  So span(V'[:, :kept]) contains every kept axis to fp64 precision: a query's
+    energy along it is screened, not dropped.  An axis whose residual is shorter than
+    AXIS_IN_SPAN lies in the span already and is left out (the next principal column stays in
+    its place); n counts the axes kept, and with n = 0 V and var come back as they are.  Any
+    orthonormal V' keeps the matcher exact; the builders check it."""
+    D = V.shape[0]
+    want = [int(k) for k in axes]
+    while True:
+        base = V[:, :kept - len(want)]
+        new, short = [], []
+        for k in want:
+            r = np.zeros(D)
+            r[k] = 1.0
+            for _ in range(2):
+                for j in range(base.shape[1]):
+                    r = r - base[:, j] * (base[:, j] @ r)
+                for u in new:
+                    r = r - u * (u @ r)
+                if np.sqrt(r @ r) < AXIS_IN_SPAN:
+                    break
+            nr = np.sqrt(r @ r)
+            if nr < AXIS_IN_SPAN:
+                short.append(k)
+            else:
+                new.append(r / nr)
+        if not short:
+            break
+        want = [k for k in want if k not in short]
+    if not new:
+        return V, var, 0
+    K = np.column_stack([base] + new)
+    # an orthonormal basis of the complement (Householder), C's principal directions inside it
+    Qc = np.linalg.qr(K, mode='complete')[0][:, kept:]
+    Uc = _eigh(Qc.T @ C @ Qc)[1]
+    Vn = np.column_stack([K, (Qc @ Uc)[:, ::-1]])
+    return Vn, np.einsum('ij,ij->j', Vn, C @ Vn), len(new)
 
 
 def rot3_rotation(db3, N):

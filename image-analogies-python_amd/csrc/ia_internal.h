@@ -349,6 +349,7 @@ struct LevelPlan {
     bool xw, r16;      // one fused launch per wave after the screen; the R16 screen and bound
     int form;          // XW_ROWS / XW_IMG / XW_STRIP, -1 without xw
     bool rk, split;    // the level has compact waves (wave_compact); two workgroups per pixel
+    bool rkcol;        // rk, and the column-0 waves are compact too (wave_compact_col)
     int tail;          // TailKind
     DbView v;          // (zeroed on LSH and simulated levels: their DBs are not the level's)
     XwVariant variant(int K, bool cmp) const { return XwVariant{form, K > 1, r16, cmp, split}; }

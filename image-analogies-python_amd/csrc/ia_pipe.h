@@ -27,6 +27,10 @@ static inline void wave_rows(int H, int W, int t, int &y_lo, int &M) {
 // initialisation noise in its window's causal part, i.e. lies in row 0 (y = 0, x = t: t <= W - 1)
 // or column 0 (x = 0: t = 3y): those queries' noise is in the dropped components
 static inline bool wave_compact(int W, int t) { return t >= W && t % 3 != 0; }
+// The other waves past row 0: t = 3y, whose only border pixel is (y, 0) (none once y is past the
+// last row).  Its noise lies on the two own-row axes (ia_rot16.h RK_AXES), so the wave may take
+// the compact screen where the level's basis keeps them (LevelPlan::rkcol)
+static inline bool wave_compact_col(int W, int t) { return t >= W && t % 3 == 0; }
 
 // the most queries of one wave, + 1 (the workspaces are sized by it)
 static inline int wave_max_queries(int H, int W) {

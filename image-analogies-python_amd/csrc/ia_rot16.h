@@ -180,6 +180,14 @@ __device__ __forceinline__ void r16_thresholds_rows(float emin, float amax0, flo
 // operands, which fill its first 8 half8: compact slot s is f16 RK_Q_F16 + s, and k^2 (fp64)
 // sits at byte RK_Q_REST_B.
 constexpr int RK_C = 24;                       // kept components
+// The feature axes the host puts into the kept span where the level takes the compact DB
+// (ia_db_rotk_span; algorithms.py compact_axes_basis): the own-row B' samples (y, x - 2) and
+// (y, x - 1).  At a column-0 pixel they reflect onto (y, 1) and (y, 0), which hold B'
+// initialisation noise at wave 3y, and they are its window's only noisy samples (the rows above
+// are synthesised): with both axes kept that noise is screened instead of dropped, so a column-0
+// query selects as few segments as a clean one (wave_compact_col, DESIGN.md §4d "Which waves")
+constexpr int RK_NAXES = 2;
+constexpr int RK_AXES[RK_NAXES] = {IA_D - 2, IA_D - 1};
 constexpr int RK_NL = 2 * R16_P, RK_M0 = RK_NL + 1, RK_NH = RK_M0 + RK_C;
 constexpr int RK_SLOTS = 32;
 constexpr int RK_TILE_H8 = RK_SLOTS / 8 * 32;  // half8 per 32-row tile (2 KiB)

@@ -1068,6 +1068,12 @@ int ia_diag_set_r16_form(int form) {
 }
 
 int ia_db_rot_components(void) { return R16_P; }
+int ia_db_rotk_span(int *kept, int *axes, int cap) {
+    if (kept) *kept = RK_BUILT ? RK_C : 0;
+    if (!RK_BUILT) return 0;
+    for (int i = 0; axes && i < RK_NAXES && i < cap; ++i) axes[i] = RK_AXES[i];
+    return RK_NAXES;
+}
 int ia_db_rot_slots(void) { return R16_SLOTS; }
 double ia_db_rot_eps_a2(void) { return R16_EPS_A2; }
 

@@ -316,6 +316,10 @@ static std::atomic<long> g_compact_min_rows{1L << 22};
 static long compact_min_rows() { return g_compact_min_rows.load(std::memory_order_relaxed); }
 // compact waves enqueued by this process (ia_diag_compact_waves: the tests' proof that the form ran)
 static std::atomic<long> g_compact_waves{0};
+// the column-0 waves (wave_compact_col) of a level whose basis keeps the own-row axes run compact
+// too (ia_diag_set_compact_col; IA_COMPACT_COL: the process's initial value, default on)
+static std::atomic<int> g_compact_col{env_int("IA_COMPACT_COL", 1) != 0};
+static bool compact_col() { return g_compact_col.load(std::memory_order_relaxed) != 0; }
 // the split tail's level threshold (rows; DESIGN.md §6b "split": a pixel's candidate segments over
 // two workgroups of k_xstrip); LONG_MAX: off (ia_diag_set_xsplit_min_rows).  2^22 rows, as the
 // compact form: c4's finest level, 1.5-1.7 % of the step on two boxes; 2^20 measured no better
@@ -399,6 +403,7 @@ int level_plan(const IaSynthArgs &a, int K, bool sim, LevelPlan *p) {
     // level, above each one's row threshold
     const bool one = l.r16 && K == 1 && !a.comm && l.form == XW_STRIP;
     l.rk = one && a.dbk && compact_level(src, l.v.sm, a.nrows);
+    l.rkcol = l.rk && a.rot_axes == RK_NAXES && compact_col();
     l.split = xsplit_grid(one, a.nrows, 1) == 2;
     return IA_OK;
 }
@@ -648,7 +653,7 @@ struct LevelRun {
         float *segmin = match_segmin(ws.scratch);
         hipEvent_t e0 = wave_event(0), e1 = wave_event(1);
         if (e0) IA_HIP(hipEventRecord(e0, sq));
-        const bool cmp = plan.rk && wave_compact(W, t);
+        const bool cmp = plan.rk && (wave_compact(W, t) || (plan.rkcol && wave_compact_col(W, t)));
         if (r16) {
             if ((rc = launch_screen16r(cmp ? a->dbk : a->dbr, v.nrows, v.sm, q16s[b], M, segmin, sq, xa.jobs, K, b,
                                        cmp)))
@@ -835,6 +840,20 @@ int ia_diag_set_graph_mode(int mode) {
 }
 
 int ia_diag_wave_compact(int W, int t) { return wave_compact(W, t) ? 1 : 0; }
+int ia_diag_wave_compact_col(int W, int t) { return wave_compact_col(W, t) ? 1 : 0; }
+
+int ia_diag_set_compact_col(int on) {
+    const int prev = compact_col() ? 1 : 0;
+    if (on == 0 || on == 1) g_compact_col.store(on);
+    return prev;
+}
+
+int ia_diag_level_compact_col(const IaSynthArgs *a, int K) {
+    IA_ARG(a && a->nrows > 0 && K >= 1, "ia_diag_level_compact_col: bad args");
+    LevelPlan p;
+    const int rc = level_plan(*a, K, false, &p);
+    return rc ? rc : (p.rkcol ? 1 : 0);
+}
 
 long ia_diag_compact_waves(void) { return g_compact_waves.load(std::memory_order_relaxed); }
 

@@ -84,6 +84,7 @@ class _LevelCall:
             a.dbr, a.rot = _ia.ptr(index.dbr).value, _ia.ptr(index.rot).value
             if getattr(index, 'dbk', None) is not None:
                 a.dbk = _ia.ptr(index.dbk).value
+                a.rot_axes = getattr(index, 'rot_axes', 0)
         a.center, a.amax = _ia.ptr(index.center).value, _ia.ptr(index.amax).value
         a.B_sm, a.B_lg = _ia.ptr(B_sm).value, _ia.ptr(B_lg).value
         a.B_hs, a.B_ws = B_sm.shape

@@ -201,6 +201,14 @@ int ia_wdist_batch(const double *a, const double *q, const double *w, int n, dou
 int ia_db_rot_applies(const IaSrcLevel *src, long row0, long nrows);
 /* the build's R16 form: components carried as split pairs (P), K-slots per row (16 per MFMA) */
 int ia_db_rot_components(void);
+/* the compact form's kept span (read only): *kept = the components its DB carries (24; 0: this
+ * build has no compact form); returns the number n of feature axes (n <= cap written to axes:
+ * 53 and 54, the own-row B' samples (y, x - 2) and (y, x - 1)) that the caller's basis should
+ * hold inside the first *kept columns where the level takes the compact DB (ia_db_rotk_applies):
+ * the last n of them, after the leading *kept - n principal directions, the remaining columns
+ * the principal directions of what is left.  A column-0 pixel's B' initialisation noise lies on
+ * those axes alone, so its wave can then take the compact screen (IaSynthArgs.rot_axes). */
+int ia_db_rotk_span(int *kept, int *axes, int cap);
 /* resources (LDS bytes per workgroup, VGPRs per lane) of a sharded level's screen (which 0:
  * the rotated k_screen16r, 1: k_screen16i) and of the fused strip kernel (rot 1: R16 form)
  * that waits for other ranks: the forward-progress rule of DESIGN.md §7
@@ -307,6 +315,10 @@ typedef struct {
      * rows (one MFMA per 16 x 16 block) and the exact stage takes their lower bounds.  Same
      * results. */
     const void *dbk;
+    /* the number of ia_db_rotk_span's axes that rot holds inside its first 24 columns (0: a
+     * plain principal basis, or unknown).  With all of them (2) and dbk, the waves whose only
+     * border pixel is a column-0 one take the compact screen too.  Same results. */
+    int rot_axes;
 } IaSynthArgs;
 /* the resources of ia_screen_resources / ia_fused_resources per level, from its IaSynthArgs as ia_synth_level would run it (the fused
  * kernel's form k_xstrip / k_xwave image / rows, or k_peer_finish without the fused kernel,

@@ -56,6 +56,16 @@ int ia_diag_screen16k(const IaSrcLevel *src, long row0, long nrows, const void *
  * previous value (0: off).  ia_diag_wave_compact: 1 iff wave t of a level W wide may take it. */
 long ia_diag_set_compact_min_rows(long rows);
 int ia_diag_wave_compact(int W, int t);
+/* the waves whose only border pixel is a column-0 one (t >= W, t = 3y; ia_diag_wave_compact_col: 1
+ * iff wave t of a level W wide is one) run compact too on a level with compact waves whose
+ * arguments say that the basis keeps both own-row axes (IaSynthArgs.rot_axes == 2,
+ * ia_db_rotk_span).  ia_diag_set_compact_col: 0 / 1 sets the switch for this process (initially
+ * IA_COMPACT_COL, default 1), any other value leaves it; returns the previous value; sampled when
+ * a level's call starts, as the thresholds are.  ia_diag_level_compact_col: 1 iff level a's
+ * column-0 waves would run compact now (K as ia_diag_level_plan), 0 if not, < 0 on an error. */
+int ia_diag_wave_compact_col(int W, int t);
+int ia_diag_set_compact_col(int on);
+int ia_diag_level_compact_col(const IaSynthArgs *a, int K);
 /* compact waves (compact screen + compact exact stage) enqueued by this process so far */
 long ia_diag_compact_waves(void);
 /* the split tail (k_xstrip with a pixel's candidate segments over two workgroups)

@@ -25,8 +25,21 @@ Queries: the 512 real finest-level queries of tests/golden/c4_queries.npz with t
 "clean" = y >= 1 and x >= 1 (no B' initialisation noise in the window's causal part).
 Segments: 4 scanlines x 128 columns (512 rows).
 
-usage: python tools/compact_study.py [C [P]]
+Kept axes (--axes): the C screened components are C - n principal directions and n feature
+axes (algorithms.compact_axes_basis, DESIGN.md §4d "Which waves"): `col` = 53, 54, the own-row B'
+samples a column-0 pixel reflects onto pixels not yet synthesised; `row` = 43..47, 50, 51, 52, the
+samples of rows y - 2 (all five) and y - 1 (x .. x + 2) a row-0 pixel reflects onto such pixels;
+`both`; or a comma-separated list.
+
+Border queries (--border N, default 64): N column-0 queries (y, 0) and N row-0 queries (0, x),
+evenly spaced, rebuilt from tests/golden/c4_full.npz: B' of level l is A'[s_l]; the state at pixel
+p is the final values before p in scanline order and initialize_Bp's values from p on.  The
+captured border queries of c4_queries.npz are rebuilt the same way first and must come out equal.
+The report is per class: clean / column-0 / row-0.
+
+usage: python tools/compact_study.py [C [P]] [--axes col|row|both|k,k,...] [--border N]
 """
+import argparse
 import os
 import sys
 import time
@@ -37,6 +50,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'oracle'))
 sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'image-analogies-python_amd'))
 
 import ia_oracle as o  # noqa: E402
 import make_config_fixtures as mf  # noqa: E402
@@ -53,9 +67,29 @@ def report(name, arr, rs):
           % (name, len(arr), arr.mean(), *np.percentile(arr, [90, 99]).astype(int), arr.max(), np.mean(mx)))
 
 
+AXES = {'col': [53, 54], 'row': [43, 44, 45, 46, 47, 50, 51, 52]}
+AXES['both'] = AXES['row'] + AXES['col']
+
+
+def border_query(B_pyr, Bp_init, Bp_final, level, px):
+    """The query row of pixel px of a level: B' final before px in scanline order, initial from it on."""
+    r, c = px
+    W = B_pyr[level].shape[1]
+    cur = Bp_init[level].copy()
+    cur.flat[:r * W + c] = Bp_final[level].flat[:r * W + c]
+    return np.hstack([o.extract_pixel_feature(B_pyr[level - 1], B_pyr[level], px, True),
+                      o.extract_pixel_feature(Bp_final[level - 1], cur, px, False)])
+
+
 def main():
-    C = int(sys.argv[1]) if len(sys.argv) > 1 else 24
-    P = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    ap = argparse.ArgumentParser()
+    ap.add_argument('C', type=int, nargs='?', default=24)
+    ap.add_argument('P', type=int, nargs='?', default=3)
+    ap.add_argument('--axes', default='')
+    ap.add_argument('--border', type=int, default=64)
+    args = ap.parse_args()
+    C, P = args.C, args.P
+    axes = AXES.get(args.axes) or [int(x) for x in args.axes.split(',') if x]
     t0 = time.time()
     A, Aps, B, k, cap, seed = mf.workload('c4')
     A_pyr, Ap_list, B_pyr, Bp_pyr, L = o.setup_luminance(A, Aps, B, cap=cap, seed=seed)
@@ -69,6 +103,11 @@ def main():
     sub = a[rs.choice(len(a), 65536, replace=False)]
     w, V = np.linalg.eigh(sub.T @ sub / len(sub))
     V = V[:, ::-1]
+    if axes:
+        import algorithms
+        Cov = sub.T @ sub / len(sub)
+        V, _, nk = algorithms.compact_axes_basis(Cov, V, w[::-1].copy(), C, axes)
+        print('kept span: %d principal directions + %d of the axes %s' % (C - nk, nk, axes))
     rho = a @ V
     var = (rho ** 2).sum(0)
     print('c4 finest DB %d rows built in %.0f s; leading 8/16/23/24/32 components hold %s of the energy'
@@ -95,6 +134,29 @@ def main():
     n = int(g['n_captured'])
     Q, px = g['q'][:n], g['pixels'][:n]
     clean = (px[:, 0] >= 1) & (px[:, 1] >= 1)
+    if args.border:
+        # B' of every level from the full run's maps, then the border queries
+        full = np.load(os.path.join(ROOT, 'tests', 'golden', 'c4_full.npz'))
+        Bp_fin = [b.copy() for b in Bp_pyr]
+        for l in range(1, L):
+            sl = full['s%d' % l].astype(np.int64)
+            Bp_fin[l] = Ap_list[0][l][sl[:, 0], sl[:, 1]].reshape(B_pyr[l].shape)
+        worst = max(np.abs(border_query(B_pyr, Bp_pyr, Bp_fin, L - 1, tuple(p)) - q).max()
+                    for p, q in zip(px[~clean], Q[~clean]))
+        print('the %d captured border queries rebuilt from c4_full.npz: largest difference %r'
+              % ((~clean).sum(), worst))
+        assert worst == 0.0
+        Hb, Wb = B_pyr[L - 1].shape
+        ys = np.linspace(1, Hb - 1, args.border).astype(int)
+        xs = np.linspace(1, Wb - 1, args.border).astype(int)
+        pcol = [(int(y), 0) for y in ys]
+        prow = [(0, int(x)) for x in xs]
+        Q = np.vstack([Q[clean]] + [border_query(B_pyr, Bp_pyr, Bp_fin, L - 1, p) for p in pcol + prow])
+        px = np.vstack([px[clean], np.array(pcol + prow)])
+        n = len(Q)
+        clean = (px[:, 0] >= 1) & (px[:, 1] >= 1)
+    col0 = (px[:, 1] == 0) & (px[:, 0] >= 1)
+    row0 = px[:, 0] == 0
     cnt = {False: [], True: []}
     dwin = []
     for m0 in range(0, n, 32):
@@ -126,7 +188,8 @@ def main():
         print('  candidate segments per query, %s rest-norm term:' % ('with the' if with_rest else 'without a'))
         report('all captured queries', arr, rs)
         report('clean-wave queries (y>=1, x>=1)', arr[clean], rs)
-        report('others (row 0 or column 0)', arr[~clean], rs)
+        report('column-0 queries (y>=1, x=0)', arr[col0], rs)
+        report('row-0 queries (y=0)', arr[row0], rs)
         if with_rest:
             # the split tail (DESIGN.md §6b "split"): arr = 1 + n (the seed and the n listed
             # segments); both workgroups rescore the seed, the slower one then ceil(n / 2) of the list
