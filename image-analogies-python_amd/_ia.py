@@ -133,6 +133,9 @@ _SIGS = {
     'ia_db3_cov': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p]),
     'ia_db3_build_rot': (ctypes.c_int, [_dp, ctypes.c_long, _dp, _dp, _dp]),
     'ia_synth3_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_long]),
+    'ia_synth3_shard_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_long,
+                                                          ctypes.c_int]),
+    'ia_level3_resources': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.POINTER(ctypes.c_int)]),
     'ia_db3_bytes': (ctypes.c_size_t, [ctypes.c_long]),
     'ia_match3_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_long]),
     'ia_match3_batch': (ctypes.c_int, [_dp, ctypes.c_long, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),

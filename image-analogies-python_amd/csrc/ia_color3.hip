@@ -21,7 +21,9 @@
 // add the 165-term distances and the B' store of all three channels.  ia_synth_levels3 runs
 // the levels pipelined; ia_synth_levels3_batch runs K jobs of identical shapes with the job as
 // a grid dimension of the R16c wave's launches (k_query3rb, k_screen3rb, k_exact3b: the same
-// bodies, per-job pointers from a device job table).  Single GPU, exact matcher.
+// bodies, per-job pointers from a device job table).  Exact matcher.  A level sharded over
+// ranks (IaSynthArgs.comm) runs the four-launch wave with k_exact3p, which publishes the
+// shard's winner, and k_peer_finish3, which collects the ranks' and finishes the pixel.
 #include "ia_common.h"
 #include "ia_internal.h"
 #include "ia_finish.h"
@@ -873,8 +875,13 @@ __global__ __launch_bounds__(256) void k_reduce3(const Best *__restrict__ part, 
     if (threadIdx.x == 0) best[blockIdx.x] = b;
 }
 
+int comm_allgather(void *comm, const void *send, void *recv, size_t bytes, hipStream_t st);   // ia_comm.hip
+int comm_nranks(void *comm);
+PeerView comm_peer_wave(void *comm);
+int comm_peer_mcap(void *comm);
+
 struct Fin3 {
-    const double *db3;       // rows of the level (row0 = 0: single GPU)
+    const double *db3;       // this rank's rows of the level (local row 0 = global row0)
     const double *q3;
     const double *Ap_lg;     // nAp x Ah x Aw x 3
     int Ah, Aw;
@@ -1039,11 +1046,13 @@ __device__ __forceinline__ unsigned long long c3_gran(unsigned tag, unsigned bit
 template <bool FUSE>
 __global__ __launch_bounds__(256) void k_exact3(Fin3 f, Scr3 sc, Nx3 nx) {
 #define C3X_BATCH 0
+#define C3X_PUB 0
 #define C3X_M nx.M
 #define C3X_YN nx.y_lo_n
 #define C3X_MN nx.M_n
 #include "ia_color3_exact.inc"
 #undef C3X_BATCH
+#undef C3X_PUB
 #undef C3X_M
 #undef C3X_YN
 #undef C3X_MN
@@ -1090,14 +1099,167 @@ __global__ __launch_bounds__(256) void k_exact3b(const C3Job *__restrict__ jobs,
     sc.nsk = J.nsk[b];
     const Nx3 &nx = J.nx[b];
 #define C3X_BATCH 1
+#define C3X_PUB 0
 #define C3X_M M
 #define C3X_YN y_lo_n
 #define C3X_MN M_n
 #include "ia_color3_exact.inc"
 #undef C3X_BATCH
+#undef C3X_PUB
 #undef C3X_M
 #undef C3X_YN
 #undef C3X_MN
+}
+
+// ---- a level whose rows are sharded over ranks (IaSynthArgs.comm) -----------
+// Each rank holds ia_db3_build(src, row0, nrows) of its contiguous row range (tiles, centre,
+// bound and A_skip its own) and runs the wave in four launches: the query rows, the screen over
+// its tiles, k_exact3p and k_peer_finish3.  k_exact3p is the exact stage above without the tail
+// (ia_color3_exact.inc, C3X_PUB): it leaves this shard's (distance, global row = row0 + local
+// row, weighted distance) in rec[m] and, on the device-side exchange (px.nranks > 0), publishes
+// it to every rank's box.  It waits for nothing.
+struct C3Pub {
+    PeerView px;             // nranks 0: RCCL (the records are all-gathered from rec)
+    ShardRec *rec;           // this rank's records of the wave (M)
+    long row0;
+};
+template <bool FUSE>   // (false: the text's FUSE branches are discarded)
+__global__ __launch_bounds__(256) void k_exact3p(Fin3 f, Scr3 sc, C3Pub pub) {
+    static_assert(!FUSE, "a sharded level runs the four-launch form");
+    const Nx3 nx{};
+#define C3X_BATCH 0
+#define C3X_PUB 1
+#define C3X_M nx.M
+#define C3X_YN nx.y_lo_n
+#define C3X_MN nx.M_n
+#include "ia_color3_exact.inc"
+#undef C3X_BATCH
+#undef C3X_PUB
+#undef C3X_M
+#undef C3X_YN
+#undef C3X_MN
+}
+
+// the replicated fp64 pyramids of a level's A side (feat3's inputs, as k_db3_build's)
+struct Src3 {
+    Img3 Asm, Alg;
+    const double *Ap_sm, *Ap_lg;
+};
+// acc8_row for a row that is not materialised here: features k = j + 8 i of DB pixel (r, c)
+// of A' image img gathered from the pyramids, exactly the values k_db3_build writes, and the
+// same sums in the same order (an accumulator that starts at +0 and adds its first term, a
+// square, holds that term's bits).  Five gathers in flight at a time, not acc8_row's 21: the
+// waiting kernel's VGPRs stay small.
+__device__ __forceinline__ Acc8 acc8_feat(const Src3 &s, int img, int r, int c, int j, const double *qs,
+                                          const double *ws) {
+    const double *psm = s.Ap_sm + (long)img * s.Asm.h * s.Asm.w * 3;
+    const double *plg = s.Ap_lg + (long)img * s.Alg.h * s.Alg.w * 3;
+    // feat3's sample of the pair (A | A' of image img; one shape) with every choice a select of
+    // scalars (feat3's own branches over two Img3 temporaries put them in scratch here)
+    auto ld = [&](int k) __attribute__((always_inline)) {
+        const bool ap = k >= D3_FULL;
+        const int kk = ap ? k - D3_FULL : k;
+        const bool co = kk < 27;                     // the coarse 3x3x3 window, else the fine 5x5x3
+        const int e = co ? kk : kk - 27;
+        const int t = e / 3, ch = e - 3 * t;
+        const int dr = co ? t / 3 - 1 : t / 5 - 2, dc = co ? t % 3 - 1 : t % 5 - 2;
+        const int h = co ? s.Asm.h : s.Alg.h, w = co ? s.Asm.w : s.Alg.w;
+        const double *p = co ? (ap ? psm : s.Asm.p) : (ap ? plg : s.Alg.p);
+        return p[((long)symi2((co ? r >> 1 : r) + dr, h) * w + symi2((co ? c >> 1 : c) + dc, w)) * 3 + ch];
+    };
+    constexpr int G = 5;   // gathers in flight
+    double hp[2], hw[2];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        double p = 0.0, w = 0.0;
+#pragma unroll 1
+        for (int g = 0; g < 10; g += G) {
+            const int k0 = j + 8 * (10 * half + g);
+            const double x0 = ld(k0), x1 = ld(k0 + 8), x2 = ld(k0 + 16), x3 = ld(k0 + 24), x4 = ld(k0 + 32);
+            auto add = [&](double xv, int k) __attribute__((always_inline)) {
+                const double d = xv - qs[k];
+                const double dw = d * ws[k];
+                p += d * d;
+                w += dw * dw;
+            };
+            add(x0, k0); add(x1, k0 + 8); add(x2, k0 + 16); add(x3, k0 + 24); add(x4, k0 + 32);
+        }
+        hp[half] = p;
+        hw[half] = w;
+    }
+    Acc8 a{hp[0], hp[1], 0.0, hw[0], hw[1], 0.0};
+    if (j < D3 - 160) {
+        const double d = ld(160 + j) - qs[160 + j];
+        const double dw = d * ws[160 + j];
+        a.pt = d * d;
+        a.wt = dw * dw;
+    }
+    return a;
+}
+
+// The tail of a sharded level, one 128-thread workgroup per pixel (modelled on k_peer_finish,
+// ia_synth.hip).  Wave 0 takes the lexicographic (distance, row) minimum of every rank's record
+// of query m: from this rank's receive box (peer_collect_rec: the ONLY inter-rank wait of the
+// colour path, with its timeout and error word; on timeout this shard's own record stands) or,
+// over RCCL (px.nranks == 0), from the gathered records rec[g * M + m].  Wave 1 meanwhile
+// computes the plain and weighted distances of the <= 15 coherence window rows, which may lie
+// in any rank's shard, from the replicated pyramids (acc8_feat: the materialised rows' bits).
+// Then c3_decide and the three-channel B' store, on replicated state: every rank ends with the
+// same B', s and im.  The wait sits here, in a small workgroup (~9 KB of LDS), never in the
+// exact stage's 256-thread, 21-23 KB ones: the screens and exact stages the awaited records
+// depend on keep room to run beside any number of these.
+__global__ __launch_bounds__(128) void k_peer_finish3(Fin3 f, Src3 src, PeerView px,
+                                                      const ShardRec *__restrict__ rec, int nranks, int M) {
+    __shared__ double qs[D3P], wsh[D3P];
+    __shared__ Acc8 cacc[15 * 8];
+    __shared__ double sump[15], sumw[15];
+    __shared__ long long rix[15];
+    __shared__ int rpos[15][3];
+    const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int y = f.y_lo + m, x = f.t - 3 * y;
+    for (int k = tid; k < D3P; k += 128) {
+        qs[k] = f.q3[(long)m * D3P + k];
+        wsh[k] = k < D3 ? f.weights[k] : 0.0;
+    }
+    if (tid < 15) c3_window(tid, y, x, f, rix, rpos);
+    XRec win{INFINITY, 0x7fffffffffffffffLL, 0.0, 0.0};
+    if (wv == 0 && px.nranks > 0) {
+        const ShardRec own = rec[m];
+        win = XRec{own.d, own.idx, own.wd, 0.0};
+    }
+    __syncthreads();
+    if (wv == 0) {
+        if (px.nranks > 0) {
+            peer_collect_rec(px, m, lane, win);
+        } else {
+            if (lane < nranks) {
+                const ShardRec r = rec[(long)lane * M + m];
+                win = XRec{r.d, r.idx, r.wd, 0.0};
+            }
+            win = xrec_wave_min(win);
+        }
+    } else {
+#pragma unroll 1
+        for (int e = lane; e < 15 * 8; e += 64) {
+            const int ro = e >> 3;
+            if (rix[ro] >= 0) cacc[e] = acc8_feat(src, rpos[ro][2], rpos[ro][0], rpos[ro][1], e & 7, qs, wsh);
+        }
+    }
+    __syncthreads();
+    if (tid < 15) {
+        if (rix[tid] >= 0) {
+            sump[tid] = sqrt(acc8_sum(cacc + 8 * tid, false));
+            const double sq = sqrt(acc8_sum(cacc + 8 * tid, true));
+            sumw[tid] = sq * sq;
+        } else {
+            sump[tid] = INFINITY;
+            sumw[tid] = 0.0;
+        }
+    }
+    __syncthreads();
+    if (wv != 0) return;
+    const long from = c3_decide(f, y, x, lane, win.i, win.wd, sump, sumw, rix, rpos);
+    if (lane < 3) f.Bp_lg[((long)y * f.W + x) * 3 + lane] = f.Ap_lg[from + lane];
 }
 
 // The per-pixel tail of the exhaustive fp64 search (IA_COLOR16=0), one 256-thread workgroup
@@ -1219,12 +1381,15 @@ struct Ws3 {
     unsigned *ctl;           // tickets[2], error word
     unsigned long long *dbox;
     C3Job *jtab;             // a batch's job table (ia_synth_levels3_batch, job 0's workspace)
+    ShardRec *rec, *rec_all; // a sharded level: this rank's records, all ranks' (RCCL gather)
 };
 // the fused colour tail (k_exact3<true>: the next wave's query rows from the exact stage's
 // launch; IA_C3_FUSE, default 1) on R16c levels; read per level (Level3::init)
 static inline bool c3_fuse() { return env_int("IA_C3_FUSE", 1) != 0; }
 static_assert(C16_TILE >= R3_TILE, "query tiles");
-static inline size_t ws3_layout(int H, int W, long nrows, char *base, Ws3 *w) {
+// (nranks > 0: a sharded level's workspace, the records after everything else, so the
+// unsharded layout and ia_synth3_workspace_bytes keep their values)
+static inline size_t ws3_layout(int H, int W, long nrows, char *base, Ws3 *w, int nranks = 0) {
     const size_t M = (size_t)wave_max_queries(H, W), Mp = (M + 31) / 32 * 32;
     size_t o = 0;
     auto take = [&](size_t bytes) { char *p = base ? base + o : nullptr; o += align_up(bytes, 256); return p; };
@@ -1241,7 +1406,11 @@ static inline size_t ws3_layout(int H, int W, long nrows, char *base, Ws3 *w) {
     char *ctl = take(256);
     char *dbox = take((size_t)H * 8 * sizeof(unsigned long long));
     char *jtab = take((size_t)IA_BATCH_MAX * sizeof(C3Job));
+    char *rec = nranks > 0 ? take(Mp * sizeof(ShardRec)) : nullptr;
+    char *rec_all = nranks > 0 ? take(Mp * (size_t)nranks * sizeof(ShardRec)) : nullptr;
     if (w) {
+        w->rec = reinterpret_cast<ShardRec *>(rec);
+        w->rec_all = reinterpret_cast<ShardRec *>(rec_all);
         w->jtab = reinterpret_cast<C3Job *>(jtab);
         w->q3b = reinterpret_cast<double *>(q3b);
         w->q16b = reinterpret_cast<half8 *>(q16b);
@@ -1259,8 +1428,9 @@ static inline size_t ws3_layout(int H, int W, long nrows, char *base, Ws3 *w) {
     return o;
 }
 
-// one 3-channel level on one GPU: the wave loop of ia_synth_level3 (per wave: the query
-// rows and split operand, the screen, the exact stage + tail; or the exhaustive fp64 search)
+// one 3-channel level (all its rows, or this rank's shard): the wave loop of ia_synth_level3
+// (per wave: the query rows and split operand, the screen, the exact stage + tail; or the
+// exhaustive fp64 search; a sharded level: wave_sharded)
 struct Level3 {
     const IaSynthArgs *a = nullptr;
     Ws3 w{};
@@ -1272,17 +1442,39 @@ struct Level3 {
     bool split = true, rot = false;   // rot: the R16c screen (a->dbr, a->rot: ia_db3_build_rot)
     bool fuse = false;                // rot with the fused tail (k_exact3<true>)
     const half8 *dbr = nullptr;
+    // a sharded level (a->comm): rows [row0, row0 + nrows) of N_total, one exchange per wave
+    bool sharded = false, peer = false;
+    int nranks = 1;
+    Src3 src3{};
     int init(const IaSynthArgs *a_, hipStream_t st) {
         a = a_;
         IA_ARG(a && a->db && a->B_sm && a->B_lg && a->Bp_sm && a->Bp_lg && a->weights && a->s && a->im &&
                    a->workspace && a->H > 0 && a->W > 0,
                "ia_synth_level3: bad args");
-        IA_ARG(!a->comm && !a->lsh && a->row0 == 0 && a->nrows == (long)a->src.nAp * a->src.Ah * a->src.Aw,
-               "ia_synth_level3: 3-channel matching runs unsharded with the exact matcher");
+        IA_ARG(!a->lsh, "ia_synth_level3: 3-channel matching runs the exact matcher (lsh must be NULL)");
+        const long N = (long)a->src.nAp * a->src.Ah * a->src.Aw;
+        sharded = a->comm != nullptr;
+        if (!sharded) {
+            IA_ARG(a->row0 == 0 && a->nrows == N,
+                   "ia_synth_level3: a partial row range (row0, nrows) needs a comm");
+        } else {
+            nranks = comm_nranks(a->comm);
+            peer = comm_peer_mcap(a->comm) > 0;
+            IA_ARG(nranks >= 1 && nranks <= 64, "ia_synth_level3: bad communicator");
+            IA_ARG(a->nrows > 0 && a->row0 >= 0 && a->row0 + a->nrows <= N && a->N_total == N,
+                   "ia_synth_level3: bad shard (row0, nrows, N_total)");
+            IA_ARG(N < (1L << 32), "ia_synth_level3: the exchange carries 32-bit rows (N_total >= 2^32)");
+            IA_ARG(g_color16.load(std::memory_order_relaxed) != 0,
+                   "ia_synth_level3: a sharded level runs the screened matcher (IA_COLOR16=0 is unsharded only)");
+            IA_ARG(!peer || comm_peer_mcap(a->comm) >= wave_max_queries(a->H, a->W),
+                   "ia_synth_level3: the peer exchange's box holds fewer queries than a wave");
+        }
         IA_ARG(!a->dbg_px == !a->dbg_dist, "ia_synth_level3: debug outputs come in pairs");
         H = a->H;
         W = a->W;
-        ws3_layout(H, W, a->nrows, reinterpret_cast<char *>(a->workspace), &w);
+        ws3_layout(H, W, a->nrows, reinterpret_cast<char *>(a->workspace), &w, sharded ? nranks : 0);
+        src3 = Src3{Img3{a->src.A_sm, a->src.A_hs, a->src.A_ws}, Img3{a->src.A_lg, a->src.Ah, a->src.Aw},
+                    a->src.Ap_sm, a->src.Ap_lg};
         nb = match3_blocks(a->nrows);
         Bsm = Img3{a->B_sm, a->B_hs, a->B_ws};
         Blg = Img3{a->B_lg, H, W};
@@ -1298,7 +1490,7 @@ struct Level3 {
         sc = Scr3{w.smin, ntiles, a->nrows, w.qn, v.meta, g_c3_stats, rot ? w.nsk : nullptr,
                   rot ? db3r_meta(const_cast<void *>(a->dbr), a->nrows) : nullptr};
         nw = wave_count(H, W);
-        fuse = rot && c3_fuse();
+        fuse = rot && c3_fuse() && !sharded;   // (a sharded level: the four-launch form)
         IA_HIP(hipMemsetAsync(w.ctl, 0, 256, st));
         if (fuse) IA_HIP(hipMemsetAsync(w.dbox, 0, (size_t)H * 8 * sizeof(unsigned long long), st));
         return IA_OK;
@@ -1369,6 +1561,7 @@ struct Level3 {
         if (K > 1) return wave_batch(t, y_lo, M, st);
         f.t = t;
         f.y_lo = y_lo;
+        if (sharded) return wave_sharded(M, st);
         if (fuse) {
             // wave t's query set b (wave 0's built here, the later ones by the previous wave's
             // k_exact3<true>), wave t + 1's into set b ^ 1
@@ -1414,6 +1607,33 @@ struct Level3 {
             k_finish3w<<<M, 256, 0, st>>>(f, w.part, nb);
         }
         IA_LAUNCH_CHECK("ia_synth_level3 wave");
+        return IA_OK;
+    }
+    // wave t of a sharded level: the query rows and the screen of this shard's tiles as on one
+    // GPU, the publishing exact stage, [RCCL: one all-gather of the M records,] the finish
+    int wave_sharded(int M, hipStream_t st) {
+        const int QT = (M + 31) / 32;
+        int tpw;
+        if (rot) {
+            const dim3 grid = screen3r_grid(ntiles, M, tpw);
+            k_query3r<<<QT * 32, 256, 0, st>>>(Bsm, Blg, Bpsm, Bplg, f.t, f.y_lo, M, v.meta, a->rot, nullptr, w.q3,
+                                               w.qn, w.nsk, w.q16);
+            k_screen3r<<<grid, 256, 0, st>>>(dbr, ntiles, w.q16, M, tpw, w.smin);
+        } else {
+            const dim3 grid = screen3_grid(ntiles, M, tpw);
+            k_query3s<<<QT * 32, 256, 0, st>>>(Bsm, Blg, Bpsm, Bplg, f.t, f.y_lo, M, v.meta, w.q3, w.qn,
+                                               reinterpret_cast<_Float16 *>(w.q16));
+            k_screen3<<<grid, 256, 0, st>>>(v.db16, ntiles, w.q16, M, tpw, w.smin);
+        }
+        const PeerView px = peer ? comm_peer_wave(a->comm) : PeerView{};
+        k_exact3p<false><<<M, 256, 0, st>>>(f, sc, C3Pub{px, w.rec, a->row0});
+        IA_LAUNCH_CHECK("ia_synth_level3 sharded wave");
+        if (!peer) {
+            const int rc = comm_allgather(a->comm, w.rec, w.rec_all, (size_t)M * sizeof(ShardRec), st);
+            if (rc) return rc;
+        }
+        k_peer_finish3<<<M, 128, 0, st>>>(f, src3, px, peer ? w.rec : w.rec_all, nranks, M);
+        IA_LAUNCH_CHECK("k_peer_finish3");
         return IA_OK;
     }
     int done(hipStream_t) { return IA_OK; }
@@ -1500,6 +1720,25 @@ int ia_match3_batch(const double *db3, long nrows, const double *q165, int M, in
 
 size_t ia_synth3_workspace_bytes(int H, int W, long nrows) { return ws3_layout(H, W, nrows, nullptr, nullptr); }
 
+size_t ia_synth3_shard_workspace_bytes(int H, int W, long nrows, int nranks) {
+    if (H <= 0 || W <= 0 || nrows <= 0 || nranks <= 0) return 0;
+    return ws3_layout(H, W, nrows, nullptr, nullptr, nranks);
+}
+
+int ia_level3_resources(const IaSynthArgs *a, int *out) {
+    IA_ARG(a && out && a->nrows > 0, "ia_level3_resources: bad args");
+    const bool rot = g_color16.load(std::memory_order_relaxed) != 0 && a->dbr && a->rot;
+    hipFuncAttributes f{}, sc{};
+    IA_HIP(hipFuncGetAttributes(&f, reinterpret_cast<const void *>(&k_peer_finish3)));
+    IA_HIP(hipFuncGetAttributes(&sc, rot ? reinterpret_cast<const void *>(&k_screen3r)
+                                         : reinterpret_cast<const void *>(&k_screen3)));
+    out[0] = (int)f.sharedSizeBytes;
+    out[1] = f.numRegs;
+    out[2] = (int)sc.sharedSizeBytes;
+    out[3] = sc.numRegs;
+    return IA_OK;
+}
+
 size_t ia_db3_rot_bytes(long nrows) { return nrows > 0 ? db3r_tiles_bytes(nrows) + sizeof(Rot3Meta) : 0; }
 
 size_t ia_db3_cov_bytes(void) {
@@ -1555,7 +1794,8 @@ int ia_synth3_status(const IaSynthArgs *levels, int n, void *stream) {
             ws3_layout(a.H, a.W, a.nrows, reinterpret_cast<char *>(a.workspace), &w);
             return w.ctl + C3_CTL_ERR;
         },
-        [](const IaSynthArgs &) { return IA_OK; });
+        // a sharded level's peer waits (k_peer_finish3) report through the exchange's error word
+        [](const IaSynthArgs &a) { return comm_peer_mcap(a.comm) > 0 ? ia_peer_status(a.comm) : IA_OK; });
 }
 
 int ia_synth_level3(const IaSynthArgs *a, void *stream) {
@@ -1617,6 +1857,15 @@ static int synth_levels3(const IaSynthArgs *levels, int n, int K, void *stream) 
     // the job tables go through this thread's pinned staging buffer (ia_pipe.h)
     C3Job *pinned = nullptr;
     if (K > 1) IA_HIP(g_pipe.staging((size_t)n * K * sizeof(C3Job), reinterpret_cast<void **>(&pinned)));
+    // Sharded levels (one exchange each) overlap over the device-side exchange, whose only
+    // waits sit in k_peer_finish3's small workgroups; over RCCL, and between ranks sharing one
+    // GPU (IA_SHARE_GPU=1), each one's first wave waits for the previous one's last, as for
+    // luminance (ia_synth.hip synth_levels)
+    static const int overlap = env_int("IA_SHARD_OVERLAP", 1) && !env_int("IA_SHARE_GPU", 0);
+    auto multi_rank = [&](const IaSynthArgs &l) {
+        if (l.comm == nullptr || l.nrows >= l.N_total) return false;
+        return !(overlap && comm_peer_mcap(l.comm) > 0);
+    };
     std::vector<Level3> run(n);
     std::vector<PipeLevel> pl(n);
     for (int j = 0; j < n; ++j) {
@@ -1624,7 +1873,7 @@ static int synth_levels3(const IaSynthArgs *levels, int n, int K, void *stream) 
             (rc = run[j].init_batch(&levels[(size_t)j * K], K, g_pipe.stream(j), pinned ? pinned + (size_t)j * K : nullptr)))
             return rc;
         // (the fused tail's launch of wave t also builds wave t + 1's query rows)
-        pl[j] = PipeLevel{run[j].H, run[j].W, run[j].fuse, false};
+        pl[j] = PipeLevel{run[j].H, run[j].W, run[j].fuse, multi_rank(levels[(size_t)j * K])};
     }
     return pipe_execute(run, pl, 1, 0, st);
 }
@@ -1633,6 +1882,9 @@ int ia_synth_levels3(const IaSynthArgs *levels, int n, void *stream) { return sy
 
 int ia_synth_levels3_batch(const IaSynthArgs *levels, int n, int K, void *stream) {
     IA_ARG(K >= 1 && K <= IA_BATCH_MAX, "ia_synth_levels3_batch: K out of range (1 .. 128)");
+    IA_ARG(levels && n >= 1 && n <= 64, "ia_synth_levels3_batch: bad level count");
+    for (size_t i = 0; i < (size_t)n * K; ++i)   // (batches shard by job, not by rows)
+        IA_ARG(!levels[i].comm, "ia_synth_levels3_batch: a batch takes no comm (sharded levels: ia_synth_levels3)");
     return synth_levels3(levels, n, K, stream);
 }
 

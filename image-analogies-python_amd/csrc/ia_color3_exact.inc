@@ -3,14 +3,20 @@
 // a kernel template <bool FUSE> with f (Fin3), sc (Scr3) and nx (Nx3) in scope and C3X_M,
 // C3X_YN, C3X_MN (the wave's M, y_lo_n, M_n) and C3X_BATCH (0 / 1) defined.  One text for both,
 // so the single job's kernel compiles exactly as it did before the batch form existed.
+// C3X_PUB (0 in those two; 1 in k_exact3p, the exact stage of a sharded level, with pub (C3Pub)
+// in scope): the coherence rows, which may lie in another rank's shard, and the tail are left
+// to k_peer_finish3; wave 0 instead stores this shard's (distance, global row, weighted
+// distance) and publishes it to every rank's box.  Nothing here waits for another rank.
     __shared__ double qs[D3P], wsh[D3P];
     __shared__ double ownv[3], nbv[3], qred[4], qds[D3];
     __shared__ int tks, anydep;
     __shared__ Acc8 acc[32 * 8];                // a tile's rows (32 x 8 parts)
+#if !C3X_PUB
     __shared__ Acc8 cacc[15 * 8];               // the coherence rows
     __shared__ double sump[15], sumw[15];
     __shared__ long long rix[15];
     __shared__ int rpos[15][3];
+#endif
     __shared__ double rd[4], rw[4];
     __shared__ long long ri[4];
     __shared__ float fmn[4];
@@ -55,7 +61,9 @@
         qs[tid] = f.q3[(long)m * D3P + tid];
         wsh[tid] = tid < D3 ? f.weights[tid] : 0.0;
     }
+#if !C3X_PUB
     if (tid < 15) c3_window(tid, y, x, f, rix, rpos);
+#endif
     const int stride = c3_stride(sc.ntiles);
     const float4 *sm4 = reinterpret_cast<const float4 *>(sc.smin + (long)m * stride);
     const int n4 = stride / 4;
@@ -124,12 +132,18 @@
         const long r0 = ntl > 0 ? (long)(full ? b : clist[b]) * 32 : 0;
         const long r = r0 + ro < sc.nrows ? r0 + ro : sc.nrows - 1;   // (rows past nrows: not taken)
         if (ntl > 0) ta = acc8_row(f.db3 + r * D3P, j, qs, wsh);
+#if !C3X_PUB
         if (b == 0 && tid < 15 * 8) {
             const long long ix = rix[ro];
             ca = acc8_row(f.db3 + (ix >= 0 ? ix : 0) * D3P, j, qs, wsh);
         }
+#endif
         acc[tid] = ta;
+#if !C3X_PUB
         if (b == 0 && tid < 15 * 8) cacc[tid] = ca;
+#else
+        (void)ca;
+#endif
         __syncthreads();
         if (j == 0 && ntl > 0 && r0 + ro < sc.nrows) {
             const double d = acc8_sum(acc + 8 * ro, false);
@@ -140,6 +154,7 @@
                 bw = sq * sq;
             }
         }
+#if !C3X_PUB
         if (b == 0 && j == 0 && tid < 15 * 8) {
             if (rix[ro] >= 0) {
                 sump[ro] = sqrt(acc8_sum(cacc + 8 * ro, false));
@@ -150,6 +165,7 @@
                 sumw[ro] = 0.0;
             }
         }
+#endif
         __syncthreads();   // acc is refilled by the next tile
     }
     for (int o = 32; o > 0; o >>= 1) {
@@ -165,6 +181,12 @@
 #pragma unroll
     for (int w = 1; w < 4; ++w)
         if (rd[w] < wd || (rd[w] == wd && ri[w] < wi)) { wd = rd[w]; wi = ri[w]; ww = rw[w]; }
+#if C3X_PUB
+    // this shard's record: kept for this rank's own finish (and the RCCL gather), and sent
+    const XRec rec{wd, pub.row0 + wi, ww, 0.0};
+    if (lane == 0) pub.rec[m] = ShardRec{rec.d, rec.i, rec.wd, 0.0};
+    if (pub.px.nranks > 0) peer_publish_rec(pub.px, m, rec, lane);
+#else
     const long src = c3_decide(f, y, x, lane, wi, ww, sump, sumw, rix, rpos);
     if (lane < 3) {
         const double val = f.Ap_lg[src + lane];
@@ -179,6 +201,7 @@
                                __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+#endif
     }   // wave 0
     }   // cur
     if constexpr (FUSE) {

@@ -9,8 +9,9 @@ exact matcher, or the LSH matcher with ``c.matcher = 'lsh'``) with the pyramids,
 
 ``synthesize_dev`` is the device-level entry used by bench.py and the parity tests:
 device pyramids in, per-level (s, im) index maps out, B' pyramid updated in place;
-with ``comm`` it shards the databases of the large levels over the ranks (RCCL all-gather
-per wave) and synthesises the small ones on every rank alone (``shard_level``).
+with ``comm`` it shards the databases of the large levels over the ranks (the device-side
+exchange or one RCCL all-gather per wave) and synthesises the small ones on every rank alone
+(``shard_level``), for luminance and 3-channel pyramids alike.
 """
 import ctypes
 import os
@@ -215,24 +216,28 @@ def _src_level3(A_sm, A_lg, Ap_sm, Ap_lg):
     return src
 
 
-def _db3_level(A_pyr, Ap_pyr_list, level):
-    """One level's 3-channel database (ia_db3_build): (A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3)."""
+def _db3_level(A_pyr, Ap_pyr_list, level, row_range=None):
+    """One level's 3-channel database (ia_db3_build): (A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3,
+    (row0, nrows)).  row_range: None (all N rows) or the (row0, nrows) of a sharded level's
+    rank, whose buffer then holds those rows alone (tiles, centre and bound its own)."""
     lib = _ia.lib()
     A_sm, A_lg = A_pyr[level - 1].contiguous(), A_pyr[level].contiguous()
     Ap_sm = torch.stack([p[level - 1] for p in Ap_pyr_list]).contiguous()
     Ap_lg = torch.stack([p[level] for p in Ap_pyr_list]).contiguous()
     src = _src_level3(A_sm, A_lg, Ap_sm, Ap_lg)
     N = src.nAp * src.Ah * src.Aw
-    db3 = torch.empty(lib.ia_db3_bytes(N) // 8, dtype=torch.float64, device=A_lg.device)
-    _ia.check(lib.ia_db3_build(ctypes.byref(src), 0, N, _ia.ptr(db3), _ia.stream()), 'ia_db3_build')
-    return A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3
+    row0, nrows = (0, N) if row_range is None else row_range
+    db3 = torch.empty(lib.ia_db3_bytes(nrows) // 8, dtype=torch.float64, device=A_lg.device)
+    _ia.check(lib.ia_db3_build(ctypes.byref(src), row0, nrows, _ia.ptr(db3), _ia.stream()), 'ia_db3_build')
+    return A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3, (row0, nrows)
 
 
-def _level3_args(built, rot, dbr, B_pyr, Bp_pyr, level, max_levels, k, weights, debug):
+def _level3_args(built, rot, dbr, B_pyr, Bp_pyr, level, max_levels, k, weights, debug, comm=None):
     """IaSynthArgs of one 3-channel level over _db3_level's database (rot, dbr: its rotated
-    form or None): (args, (s, im, debug record or None), buffers to keep alive)."""
+    form or None): (args, (s, im, debug record or None), buffers to keep alive).  comm: the
+    exchange of a sharded level (the database is then this rank's row range), else None."""
     lib = _ia.lib()
-    A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3 = built
+    A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3, (row0, nrows) = built
     dev = A_lg.device
     B_sm, B_lg = B_pyr[level - 1].contiguous(), B_pyr[level].contiguous()
     Bp_sm, Bp_lg = Bp_pyr[level - 1], Bp_pyr[level]
@@ -244,10 +249,14 @@ def _level3_args(built, rot, dbr, B_pyr, Bp_pyr, level, max_levels, k, weights, 
     if debug:
         dbg = (torch.zeros((H * W, 7), dtype=torch.int32, device=dev),
                torch.zeros((H * W, 2), dtype=torch.float64, device=dev))
-    ws = _ia.workspace(lib.ia_synth3_workspace_bytes(H, W, N))
+    if comm is None:
+        ws = _ia.workspace(lib.ia_synth3_workspace_bytes(H, W, nrows))
+    else:
+        ws = _ia.workspace(lib.ia_synth3_shard_workspace_bytes(H, W, nrows, lib.ia_comm_nranks(comm)))
     a = _ia.IaSynthArgs()
     a.src = src
-    a.db, a.row0, a.nrows, a.N_total = _ia.ptr(db3).value, 0, N, N
+    a.db, a.row0, a.nrows, a.N_total = _ia.ptr(db3).value, row0, nrows, N
+    a.comm = comm
     a.B_sm, a.B_lg = _ia.ptr(B_sm).value, _ia.ptr(B_lg).value
     a.B_hs, a.B_ws = B_sm.shape[:2]
     a.H, a.W = H, W
@@ -262,8 +271,16 @@ def _level3_args(built, rot, dbr, B_pyr, Bp_pyr, level, max_levels, k, weights, 
     return a, (s, im, dbg), (B_sm, B_lg, ws)
 
 
+def level3_resources(args):
+    """level_resources for a 3-channel level (ia_level3_resources): k_peer_finish3, the only
+    kernel of a sharded colour level that waits for other ranks, and the screen it launches."""
+    out = (ctypes.c_int * 4)()
+    _ia.check(_ia.lib().ia_level3_resources(ctypes.byref(args), out), 'ia_level3_resources')
+    return (out[0], out[1]), (out[2], out[3])
+
+
 def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, levels=None,
-                    debug=False, pipeline=None):
+                    debug=False, pipeline=None, comm=None, rank=0, nranks=1):
     """3-channel synthesis (num_ch = 3: convert=False on colour images, 165-dim rows): per
     level the materialised fp64 database (ia_db3_build), and by default (IA_DB_ROT) its
     rotated split-f16 form (R16c, DESIGN.md §4e: ia_db3_build_rot under ONE rotation for all
@@ -273,7 +290,13 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
     next wave's rotated query rows).  IA_DB_ROT=0: the split-f16 screen k_screen3 and the
     unfused exact stage (§4c).  pipeline (default pipeline_default()): the levels run
     concurrently (ia_synth_levels3), else one after the other (ia_synth_level3); the same
-    results.  Same return value as synthesize_dev."""
+    results.  comm, rank, nranks: as synthesize_dev, with the same policy: the levels of
+    shard_level(level_rows, nranks) are sharded (each rank builds and screens
+    shard_rows(N, rank, nranks) alone; per wave k_exact3p publishes the shard's winner and
+    k_peer_finish3 collects every rank's and finishes the pixel) and the others
+    run replicated; pipelined sharded levels need one exchange each, and with nranks > 1 on the
+    device-side exchange sharded_schedule decides from ia_level3_resources whether they may
+    overlap.  Same return value as synthesize_dev."""
     lib = _ia.lib()
     st = _ia.stream()
     weights = weights if torch.is_tensor(weights) else _ia.to_dev(weights)
@@ -281,7 +304,20 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
         pipeline = pipeline_default()
     out, args, keep, done = {}, [], [], []
     todo = [l for l in range(1, max_levels) if levels is None or l in levels]
-    built = {level: _db3_level(A_pyr, Ap_pyr_list, level) for level in todo}
+    comms = list(comm) if isinstance(comm, (list, tuple)) else None
+    sharded = [l for l in todo if comm is not None and shard_level(level_rows(Ap_pyr_list, l), nranks)]
+    if pipeline and len(sharded) > 1 and (comms is None or len(comms) < len(sharded)):
+        pipeline = False    # one exchange cannot serve two levels running at once
+    peer_rule = (sharded and nranks > 1 and _ia.exchange_kind() == 'peer' and torch.cuda.is_available())
+
+    def level_comm(level):
+        if level not in sharded:
+            return None
+        return comms[min(sharded.index(level), len(comms) - 1)] if comms else comm
+    built = {level: _db3_level(A_pyr, Ap_pyr_list, level,
+                               shard_rows(level_rows(Ap_pyr_list, level), rank, nranks) if level in sharded
+                               else None)
+             for level in todo}
     # the rotated split screen (R16c), bit-identical results: one rotation for every level,
     # the principal directions of the finest level's rows (IA_ROT3_SHARED, default 1: one
     # device sync and one 165 x 165 eigh per call instead of one per level; the coarser
@@ -289,17 +325,31 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
     # the matcher exact); 0: each level its own
     shared = None
     if _ia.db_rot_enabled() and todo and os.environ.get('IA_ROT3_SHARED', '1') != '0':
-        _, _, _, _, _, Nf, db3f = built[todo[-1]]
-        shared = algorithms.rot3_rotation(db3f, Nf)
+        # (of this rank's rows of it, where that level is sharded: the ranks need not agree)
+        db3f, (_, nf) = built[todo[-1]][6:8]
+        shared = algorithms.rot3_rotation(db3f, nf)
+    prepared = []
     for level in todo:
-        A_sm, A_lg, Ap_sm, Ap_lg, src, N, db3 = built[level]
+        db3, (_, nrows) = built[level][6:8]
         rot = dbr = None
         if shared is not None:
-            rot, dbr = shared, algorithms.rot3_apply(db3, N, shared)
+            rot, dbr = shared, algorithms.rot3_apply(db3, nrows, shared)
         elif _ia.db_rot_enabled():
-            rot, dbr = algorithms.rot3_build(db3, N)
-        a, (s, im, dbg), (B_sm, B_lg, ws) = _level3_args(built[level], rot, dbr, B_pyr, Bp_pyr, level,
-                                                         max_levels, k, weights, debug)
+            rot, dbr = algorithms.rot3_build(db3, nrows)
+        prepared.append((level, rot, dbr) + _level3_args(built[level], rot, dbr, B_pyr, Bp_pyr, level, max_levels,
+                                                         k, weights, debug, level_comm(level)))
+    if peer_rule:
+        # k_peer_finish3's waiting workgroups must leave room for the screens
+        res = [level3_resources(p[3]) for p in prepared if p[0] in sharded]
+        share = nranks if os.environ.get('IA_SHARE_GPU', '0') == '1' else 1
+        cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+        pipeline = sharded_schedule([tuple(B_pyr[l].shape[:2]) for l in sharded], pipeline, share,
+                                    [r[0] for r in res], [r[1] for r in res], cus)
+        if os.environ.get('IA_VERBOSE'):
+            print('[ia] sharded colour levels %s: kernels %s, pipelined %s' % (sharded, res, pipeline),
+                  file=sys.stderr, flush=True)
+    for level, rot, dbr, a, (s, im, dbg), (B_sm, B_lg, ws) in prepared:
+        A_sm, A_lg, Ap_sm, Ap_lg, _, _, db3, _ = built[level]
         done.append((a, (A_sm, A_lg, Ap_sm, Ap_lg, B_sm, B_lg, db3, ws, rot, dbr)))
         if not pipeline:
             _ia.check(lib.ia_synth_level3(ctypes.byref(a), st), 'ia_synth_level3')
@@ -392,11 +442,11 @@ def synthesize_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights,
     a later pipelined call of the same thread then waits for it to end before it enqueues
     (IA_PIPE_DRAIN).  Returns {level: (s, im[, debug])} device tensors."""
     if B_pyr[-1].dim() == 3:     # 3-channel matching (num_ch = 3)
-        if comm is not None or nranks > 1 or lsh is not None:
-            raise NotImplementedError('3-channel matching runs on one GPU with the exact matcher')
+        if lsh is not None:
+            raise NotImplementedError('3-channel matching runs the exact matcher')
         return synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights,
                                levels=levels, debug=debug,
-                               pipeline=False if eager else pipeline)
+                               pipeline=False if eager else pipeline, comm=comm, rank=rank, nranks=nranks)
     w = weights if torch.is_tensor(weights) else _ia.to_dev(weights)
     if pipeline is None:
         pipeline = pipeline_default() and not eager

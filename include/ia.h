@@ -245,19 +245,32 @@ int ia_db_build_rotk(const IaSrcLevel *src, long row0, long nrows, const double 
  *   ia_db3_bytes) of rows [row0, row0 + nrows).
  * ia_level_features3_f64: compute_feature_array (algorithms.py:11-47) of one level pair,
  *   h*w x 102 (full) or x 63 (half).
- * ia_synth_level3: one level on one GPU with the exact matcher (the split-f16 MFMA screen
+ * ia_synth_level3: one level with the exact matcher (the split-f16 MFMA screen
  *   k_screen3 and an exact fp64 rescore of its candidate tiles in the oracle's order;
  *   IA_COLOR16=0: exhaustive fp64 search of the materialised rows), the coherence / kappa
- *   tail and the 3-channel B' update; a->db = ia_db3_build output over all rows; workspace
- *   of ia_synth3_workspace_bytes.
+ *   tail and the 3-channel B' update.  comm NULL: a->db = ia_db3_build output over all rows
+ *   (row0 0, nrows = N_total), workspace of ia_synth3_workspace_bytes.  comm set (an
+ *   ia_comm_init communicator or an ia_peer_* exchange): the level is sharded; a->db, a->dbr
+ *   are ia_db3_build(src, row0, nrows) / ia_db3_build_rot of this rank's rows alone, N_total
+ *   all rows (< 2^32), workspace of ia_synth3_shard_workspace_bytes.  Per wave the exact stage
+ *   then publishes this shard's (distance, global row, weighted distance) (device-side
+ *   exchange) or leaves it for one all-gather (RCCL), and k_peer_finish3 takes the minimum over
+ *   the ranks and finishes the pixel from the replicated pyramids: every rank ends with the
+ *   same B', s, im, bit-identical to the unsharded run.  IA_E_ARG for a sharded level with lsh,
+ *   with IA_COLOR16=0, or with N_total >= 2^32.
  * ia_synth_levels3: n consecutive 3-channel levels at once, pipelined as ia_synth_levels
  *   (one stream per level, wave t of level j behind the waves of level j-1 its coarse
- *   windows read); the same results as n ia_synth_level3 calls in order. */
+ *   windows read); the same results as n ia_synth_level3 calls in order.  Sharded levels need
+ *   one communicator each; over RCCL they run one at a time. */
 size_t ia_db3_bytes(long nrows);
 int ia_db3_build(const IaSrcLevel *src, long row0, long nrows, double *db3, void *stream);
 int ia_level_features3_f64(const double *sm, int hs, int ws, const double *lg, int h, int w,
                            int full, double *out, void *stream);
 size_t ia_synth3_workspace_bytes(int H, int W, long nrows);
+/* the workspace of a sharded 3-channel level (IaSynthArgs.comm set): that of
+ * ia_synth3_workspace_bytes for this rank's nrows, then this rank's records of a wave and, for
+ * the RCCL all-gather, the nranks ranks' */
+size_t ia_synth3_shard_workspace_bytes(int H, int W, long nrows, int nranks);
 /* the per-pixel API for 165-dim rows: exact 1-NN of M queries (M x 165) over the
  * materialised rows (workspace of ia_match3_workspace_bytes), the coherence argmin over n
  * <= 64 candidate rows (n x 165) and weighted distances (n pairs of 165-dim rows) */
@@ -276,7 +289,9 @@ int ia_wdist3_batch(const double *a, const double *q, const double *w, int n, do
  * kappa_factor = 1 + 2**(level - max_levels) * k.
  * comm: NULL (single GPU) or an ia_comm_init() communicator — the DB rows are then
  * sharded (row0/nrows of this rank, N_total overall) and each wave exchanges the per-rank
- * (dist, idx, weighted dist) winners with one RCCL all-gather (exact matcher only). */
+ * (dist, idx, weighted dist) winners with one RCCL all-gather (exact matcher only).  Luminance
+ * (ia_synth_level / ia_synth_levels) and 3-channel levels (ia_synth_level3 / ia_synth_levels3)
+ * both take it; the batch entries (ia_synth_levels_batch, ia_synth_levels3_batch) do not. */
 typedef struct {
     IaSrcLevel src;
     const void *db; long row0, nrows, N_total;
@@ -325,13 +340,19 @@ typedef struct {
  * and the screen: k_screen16r where the level has the rotated DB, else the 4-wave split-f16
  * screen of its DB form): out = {waiting kernel LDS bytes, VGPRs, screen LDS bytes, VGPRs} */
 int ia_level_resources(const IaSynthArgs *a, int *out);
+/* ia_level_resources for a 3-channel level as ia_synth_level3 would run it: out = {waiting
+ * kernel LDS bytes, VGPRs, screen LDS bytes, VGPRs}: k_peer_finish3 (the only kernel of a
+ * sharded colour level that waits for other ranks) and the screen the level launches
+ * (k_screen3r with dbr / rot, else k_screen3) */
+int ia_level3_resources(const IaSynthArgs *a, int *out);
 #define IA_SYNTH_EAGER 1
 #define IA_SYNTH_PROF 2
 size_t ia_synth_workspace_bytes(int H, int W, long nrows, int nranks);
 int ia_synth_level(const IaSynthArgs *a, void *stream);
 int ia_synth_level3(const IaSynthArgs *a, void *stream);
 /* after ia_synth_level3 / ia_synth_levels3 of these levels: synchronises the stream and returns
- * IA_E_SCHED if a wait for a neighbouring pixel's decision timed out in the fused colour tail */
+ * IA_E_SCHED if a wait for a neighbouring pixel's decision timed out in the fused colour tail,
+ * IA_E_TIMEOUT if another rank's records never came to a sharded level's device-side exchange */
 int ia_synth3_status(const IaSynthArgs *levels, int n, void *stream);
 int ia_synth_levels3(const IaSynthArgs *levels, int n, void *stream);
 /* K independent 3-channel jobs of identical shapes (the multi_script batch with convert=False,
@@ -343,8 +364,8 @@ int ia_synth_levels3(const IaSynthArgs *levels, int n, void *stream);
  * equal K separate ia_synth_levels3 calls; ia_synth3_status takes all n * K args.
  * 1 <= K <= 128; K = 1 is ia_synth_levels3.  IA_E_ARG (nothing launched) when the jobs differ
  * in a shape (H, W, B_hs, B_ws, src.Ah / Aw / A_hs / A_ws / nAp, nrows), in having debug
- * outputs or dbr / rot, when a job has a comm, an lsh or a partial row range, and when K > 1
- * without the rotated DB (the batch form exists for the R16c screen only). */
+ * outputs or dbr / rot, when a job has a comm (for any K: batches shard by job), an lsh or a
+ * partial row range, and when K > 1 without the rotated DB (the batch form exists for the R16c screen only). */
 int ia_synth_levels3_batch(const IaSynthArgs *levels, int n, int K, void *stream);
 /* the rotated split screen for 3-channel rows (R16c): after ia_db3_build, the
  * caller takes the principal directions V of the level's centred rows (165 x 165, columns by

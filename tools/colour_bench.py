@@ -8,6 +8,13 @@ usage: python tools/colour_bench.py [H W] [steps] [jobs]   (default 180 117 (c1 
        synthesize_batch_dev call (ia_synth_levels3_batch): ms per step and per job, every
        step's time, the candidate tiles per query, under one rotation per batch and one per
        job (IA_ROT3_BATCH_SHARED both ways)
+       python tools/colour_bench.py H W steps --shards G [G ...]
+       the per-rank cost of the sharded colour synthesis in the manner of tools/shard_sim.py: rank
+       0 of G row shards (every level sharded: IA_SHARD_MIN_ROWS defaults to 0 here) over a 1-rank
+       exchange (IA_EXCHANGE: peer [default] or rccl), so each wave runs the sharded path (query
+       rows, the screen of the shard's tiles, k_exact3p, k_peer_finish3) without another rank's
+       latency.  B' is the shard's own: timing only.  Per G: ms per level (levels one at a time,
+       the median of `steps`) and ms per pipelined step
        COLOUR_PIPE=0: the colour levels one at a time (default: pipelined, ia_synth_levels3)
        COLOUR_ONLY=1: the 3-channel run alone (kernel traces of it)
 Also reports the colour exact stage's candidate tiles per query (ia_diag_color16_stats) and a
@@ -82,9 +89,62 @@ def batch_main(H, W, steps, K):
     print(json.dumps(out))
 
 
+def shards_main(H, W, steps, gs):
+    """Rank 0 of G shards of every colour level over a 1-rank exchange, for each G."""
+    import _ia
+    from scipy.ndimage import gaussian_filter
+    os.environ.setdefault('IA_SHARD_MIN_ROWS', '0')
+    dev = 'cuda:0'
+    A = np.dstack([bench.smooth_noise(7 + 17 * c, (H, W)) for c in range(3)])
+    Ap = np.dstack([gaussian_filter(A[..., c], 1.5) for c in range(3)])
+    B = np.dstack([bench.smooth_noise(8 + 17 * c, (H, W)) for c in range(3)])
+    a, ap, b = (torch.as_tensor(x).to(dev) for x in (A, Ap, B))
+    w = torch.as_tensor(cfg.compute_weights(3, 5, 12, 3)).to(dev)
+    nB = ip.num_layers(H, W, cfg.n_sm, None)
+    L = nB + 1
+    shapes = [(H, W, 3)]
+    for _ in range(nB):
+        shapes.append(((shapes[-1][0] + 1) // 2, (shapes[-1][1] + 1) // 2, 3))
+    shapes.reverse()
+    init = [torch.as_tensor(x).to(dev) for x in ip.initialize_Bp([np.empty(s) for s in shapes], True, 9)]
+    Bp = [x.clone() for x in init]
+    A_pyr, Ap_pyr, B_pyr = (ip.gaussian_pyramid_dev(x, cfg.n_sm) for x in (a, ap, b))
+    comms = [_ia.exchange(0, 1) for _ in range(1, L)]
+    out = {'size': [H, W], 'steps': steps, 'exchange': _ia.exchange_kind(),
+           'rows': {l: ia.level_rows([Ap_pyr], l) for l in range(1, L)}, 'shards': {}}
+
+    def timed(**kw):
+        for d, s in zip(Bp, init):
+            d.copy_(s)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ia.synthesize_dev(A_pyr, [Ap_pyr], B_pyr, Bp, L, 0.5, w, rank=0, **kw)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    try:
+        for G in gs:
+            timed(comm=comms, nranks=G, pipeline=True)        # warm-up
+            levels = {l: float(np.median([timed(comm=comms[0], nranks=G, levels={l}, pipeline=False)
+                                          for _ in range(steps)])) for l in range(1, L)}
+            pipe = [timed(comm=comms, nranks=G, pipeline=True) for _ in range(steps)]
+            out['shards'][G] = {'ms_per_level': {l: round(t, 3) for l, t in levels.items()},
+                                'ms_levels_sum': round(sum(levels.values()), 3),
+                                'ms_per_step_pipelined': round(float(np.median(pipe)), 3),
+                                'ms_steps': [round(t, 3) for t in pipe]}
+        for cm in comms:
+            _ia.exchange_status(cm)
+    finally:
+        torch.cuda.synchronize()
+        for cm in comms:
+            _ia.lib().ia_comm_destroy(cm)
+    print(json.dumps(out))
+
+
 def main():
     H, W = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (180, 117)
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    if '--shards' in sys.argv:
+        return shards_main(H, W, steps, [int(g) for g in sys.argv[sys.argv.index('--shards') + 1:]] or [1, 2, 4, 8])
     if len(sys.argv) > 4 and int(sys.argv[4]) > 1:
         return batch_main(H, W, steps, int(sys.argv[4]))
     from scipy.ndimage import gaussian_filter
