@@ -154,6 +154,10 @@ _SIGS = {
     'ia_lsh_build': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long, _dp,
                                     ctypes.POINTER(IaLsh), _dp]),
     'ia_lsh_bits': (ctypes.c_int, [ctypes.c_long]),
+    'ia_lsh3_bytes': (ctypes.c_size_t, [ctypes.c_long, ctypes.c_int]),
+    'ia_lsh3_build': (ctypes.c_int, [_dp, ctypes.c_long, _dp, ctypes.POINTER(IaLsh), _dp]),
+    'ia_lsh3_match_batch': (ctypes.c_int, [_dp, ctypes.c_long, _dp, ctypes.POINTER(IaLsh), _dp,
+                                           ctypes.c_int, _dp, _dp, _dp]),
     'ia_comm_unique_id': (ctypes.c_int, [ctypes.c_char_p]),
     'ia_comm_init': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
                                     ctypes.POINTER(ctypes.c_void_p)]),

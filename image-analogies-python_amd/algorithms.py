@@ -6,7 +6,8 @@
                             screening database (ia_db_build, a10); returns
                             (index handles, params, As, As_size) like the reference
     best_approximate_match  ia_match_batch on one query (a11) — EXACT 1-NN, where the
-                            reference asks FLANN's randomized kd-tree
+                            reference asks FLANN's randomized kd-tree (c.matcher = 'lsh':
+                            the approximate LSH matcher, 55- and 165-dim rows alike)
     best_coherence_match    candidate bookkeeping as the reference + ia_coherence_pick (a13)
     compute_distance        ia_wdist_batch (a14)
 
@@ -61,14 +62,16 @@ def compute_feature_array(im_pyr, c, full_feat):
 
 # ---- the level database (index) ---------------------------------------------------------------
 
-def lsh_projections(tables, hashes, width, seed=0):
+def lsh_projections(tables, hashes, width, seed=0, dim=55):
     """E2LSH parameters (host): (tables*hashes, 56) float32 rows, p ~ N(0, I_55) in
-    elements 0..54 and the offset b ~ U[0, width) in element 55."""
+    elements 0..54 and the offset b ~ U[0, width) in element 55.  dim=165 (3-channel rows):
+    rows of 168 floats, p in elements 0..164, b in element 165, zeros after."""
     rs = np.random.RandomState(seed)
     n = int(tables) * int(hashes)
-    P = np.zeros((n, _ia.IA_DP), dtype=np.float32)
-    P[:, :55] = rs.standard_normal((n, 55))
-    P[:, 55] = rs.uniform(0.0, width, n)
+    dim = int(dim)
+    P = np.zeros((n, (dim + 1 + 3) // 4 * 4), dtype=np.float32)
+    P[:, :dim] = rs.standard_normal((n, dim))
+    P[:, dim] = rs.uniform(0.0, width, n)
     return P
 
 
@@ -326,11 +329,40 @@ def rot3_build(db3, N):
     return rot, rot3_apply(db3, N, rot)
 
 
+def lsh3_tables(A_lg, Ap_lg, db3, N, tables=16, hashes=4, width=1.0, seed=0):
+    """The LSH tables of a 3-channel level's N materialised rows (db3: its ia_db3_build
+    buffer; A_lg (h, w, 3) and Ap_lg (nAp, h, w, 3): the level's fine images).  The centre is
+    mean(A_lg) for the 102 A dims and mean(Ap_lg) for the 63 A' dims, the bucket width
+    ``width`` x max(sqrt((102 var(A_lg) + 63 var(Ap_lg)) / 165), 1e-6), the projections
+    lsh_projections(..., dim=165).  Returns (IaLsh, centre (165, device), the projections on
+    the host and on the device, the tables' memory); the IaLsh points into the last two."""
+    dev = A_lg.device
+    L, k = int(tables), int(hashes)
+    if not (1 <= L and 1 <= k and L * k <= 64):
+        raise ValueError('LSH needs 1 <= tables * hashes <= 64')
+    c = np.empty(165)
+    c[:102] = _ia.mean_dev(A_lg)
+    c[102:] = _ia.mean_dev(Ap_lg)
+    center = torch.as_tensor(c).to(dev)
+    var = (102 * _ia.var_f64(A_lg) + 63 * _ia.var_f64(Ap_lg)) / 165.0
+    w = float(width) * max(np.sqrt(var), 1e-6)
+    proj_host = lsh_projections(L, k, w, seed, dim=165)
+    proj = torch.as_tensor(proj_host).to(dev)
+    lib = _ia.lib()
+    mem = _ia.workspace(lib.ia_lsh3_bytes(N, L))
+    h = _ia.IaLsh()
+    h.mem, h.proj, h.L, h.k, h.w = _ia.ptr(mem).value, _ia.ptr(proj).value, L, k, w
+    _ia.check(lib.ia_lsh3_build(_ia.ptr(db3), N, _ia.ptr(center), ctypes.byref(h), _ia.stream()),
+              'ia_lsh3_build')
+    return h, center, proj_host, proj, mem
+
+
 class LevelIndex3:
     """As[level] for 3-channel images (num_ch = 3): the materialised fp64 rows
     [A full | A'_i half], 165 values each (ia_db3_build, which also builds the split-f16
     rows of the synthesis screen after them), searched exhaustively in fp64
-    (ia_match3_batch) — exact like LevelIndex."""
+    (ia_match3_batch) — exact like LevelIndex; build_lsh() switches it to the approximate
+    LSH matcher (ia_lsh3_build / ia_lsh3_match_batch)."""
 
     def __init__(self, A_sm, A_lg, Ap_sm, Ap_lg):
         self.A_sm, self.A_lg = A_sm.contiguous(), A_lg.contiguous()
@@ -349,7 +381,7 @@ class LevelIndex3:
                                device=A_lg.device)
         _ia.check(lib.ia_db3_build(ctypes.byref(src), 0, self.N, _ia.ptr(self.db3), _ia.stream()),
                   'ia_db3_build')
-        self.lsh = None
+        self.lsh = self.center = None
         self.rot = self.dbr = None
 
     def build_rot(self):
@@ -357,8 +389,22 @@ class LevelIndex3:
         self.rot, self.dbr = rot3_build(self.db3, self.N)
         return self
 
+    def build_lsh(self, tables=16, hashes=4, width=1.0, seed=0):
+        """Switch this index to the approximate LSH matcher (c.matcher = 'lsh'), as
+        LevelIndex.build_lsh with 165-dim rows: the centre is the mean of A (all three
+        channels; the 102 A dims) and of the A' images (the 63 A' dims), the bucket width
+        ``width`` x the RMS per-dimension spread estimated from the pixel variances, the
+        tables ia_lsh3_build's over the materialised rows."""
+        (self.lsh, self.center, self.lsh_proj_host, self.lsh_proj,
+         self.lsh_mem) = lsh3_tables(self.A_lg, self.Ap_lg, self.db3, self.N, tables, hashes, width, seed)
+        return self
+
+    def lsh_ptr(self):
+        return ctypes.pointer(self.lsh) if self.lsh is not None else None
+
     def match(self, Q, exact=None):
-        """1-NN rows (global index, fp64 distance) of queries Q (M x 165)."""
+        """1-NN rows (global index, fp64 distance) of queries Q (M x 165): exact, or from
+        the LSH buckets when build_lsh() was called (``exact=True`` forces exact)."""
         dev = self.A_lg.device
         Q = torch.as_tensor(Q, dtype=torch.float64)
         if Q.dim() == 1:
@@ -367,6 +413,11 @@ class LevelIndex3:
         M = Q.shape[0]
         idx = torch.empty(M, dtype=torch.int64, device=dev)
         dist = torch.empty(M, dtype=torch.float64, device=dev)
+        if not exact and self.lsh is not None:
+            _ia.check(_ia.lib().ia_lsh3_match_batch(_ia.ptr(self.db3), self.N, _ia.ptr(self.center),
+                                                    self.lsh_ptr(), _ia.ptr(Q), M, _ia.ptr(idx),
+                                                    _ia.ptr(dist), _ia.stream()), 'ia_lsh3_match_batch')
+            return idx, dist
         ws = _ia.workspace(_ia.lib().ia_match3_workspace_bytes(M, self.N))
         _ia.check(_ia.lib().ia_match3_batch(_ia.ptr(self.db3), self.N, _ia.ptr(Q), M, _ia.ptr(idx),
                                             _ia.ptr(dist), _ia.ptr(ws), _ia.stream()),
@@ -426,13 +477,14 @@ def create_index(A_pyr, Ap_pyr_list, c):
     A_dev = [_ia.to_dev(p) for p in A_pyr]
     Ap_dev = [[_ia.to_dev(p) for p in pyr] for pyr in Ap_pyr_list]
     lsh = lsh_params(c)
-    if A_dev[0].dim() == 3:      # 3 channels: materialised rows, exact search
-        if lsh is not None:
-            raise NotImplementedError('3-channel matching runs with the exact matcher only')
+    if A_dev[0].dim() == 3:      # 3 channels: materialised rows, exact search or LSH
         index = [None] + [LevelIndex3(A_dev[l - 1], A_dev[l],
                                       torch.stack([p[l - 1] for p in Ap_dev]),
                                       torch.stack([p[l] for p in Ap_dev]))
                           for l in range(1, c.max_levels)]
+        if lsh is not None:
+            for ix in index[1:]:
+                ix.build_lsh(**lsh)
     else:
         index = create_index_dev(A_dev, Ap_dev, c.max_levels, lsh=lsh)
     if lsh is None:

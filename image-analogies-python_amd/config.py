@@ -11,7 +11,9 @@ longer accepts as indices).  Fields added by this build (SURV
     matcher  'brute': exact 1-NN (split-f16 MFMA screen + fp64 rescore), the default;
              'lsh': approximate E2LSH matcher with
              lsh_tables x lsh_hashes projections, bucket width lsh_width (in units of
-             the rows' RMS per-dimension spread) and projection seed lsh_seed
+             the rows' RMS per-dimension spread) and projection seed lsh_seed;
+             for luminance and for 3-channel matching (convert=False on colour images)
+             alike, on one GPU (sharded levels run the exact matcher)
 """
 import numpy as np
 

@@ -21,7 +21,9 @@
 // add the 165-term distances and the B' store of all three channels.  ia_synth_levels3 runs
 // the levels pipelined; ia_synth_levels3_batch runs K jobs of identical shapes with the job as
 // a grid dimension of the R16c wave's launches (k_query3rb, k_screen3rb, k_exact3b: the same
-// bodies, per-job pointers from a device job table).  Exact matcher.  A level sharded over
+// bodies, per-job pointers from a device job table).  The exact matcher is the default; an
+// unsharded level with IaSynthArgs.lsh runs the approximate one (k_query3, then k_lsh3_pixel
+// over ia_lsh3_build's tables: ia_lsh.hip's definition with D = 165).  A level sharded over
 // ranks (IaSynthArgs.comm) runs the four-launch wave with k_exact3p, which publishes the
 // shard's winner, and k_peer_finish3, which collects the ranks' and finishes the pixel.
 #include "ia_common.h"
@@ -1140,6 +1142,172 @@ __global__ __launch_bounds__(256) void k_exact3p(Fin3 f, Scr3 sc, C3Pub pub) {
 #undef C3X_MN
 }
 
+// ---- the LSH matcher for 165-dim rows (c.matcher = 'lsh' with convert=False) ---------------
+// The definition of ia_lsh.hip with D = 165 over the materialised fp64 rows: tables from
+// ia_lsh3_build (Lsh3View), centred value fl32(q_k - c_k), hash floorf(d / w) with d from
+// p[165] through fmaf(p[e], q'[e], d), e = 0..164 in order, key = the masked sum of lsh_mix.
+// One 256-thread workgroup per pixel of the wave (the shape of k_exact3<false>): the query row,
+// weights and coherence window in one round trip; the L k hashes, one lane each (the 672-B
+// projection rows as float4s, 16-B aligned); per table the bucket range (an empty bucket: the 4
+// sorted entries around its position) and a prefix of the candidate counts (<= LSH_CAP per
+// table); then the candidates in passes of 32 rows, 8 threads per row through acc8_row (plain
+// and weighted sums from one read), the 15 coherence rows in the first pass, each pass's row
+// numbers loaded during the pass before; the block's lexicographic (distance, row) minimum
+// (no valid candidate: row 0, as k_lsh_query's row0), c3_decide and the 3-channel B' store.
+// It waits for nothing and builds no query rows: a wave is k_query3, then this kernel.
+// TAIL false: the stand-alone query (ia_lsh3_match_batch): query m from f.q3 + m qstride, the
+// winner to idx / dist, no window, weights or tail.
+template <bool TAIL>
+__global__ __launch_bounds__(256) void k_lsh3_pixel(Fin3 f, Lsh3View lv, const double *__restrict__ center,
+                                                    long nrows, int qstride, int64_t *__restrict__ idx,
+                                                    double *__restrict__ dist) {
+    __shared__ double qs[D3P], wsh[D3P];
+    __shared__ __attribute__((aligned(16))) float qc[D3P];
+    __shared__ unsigned int hk[LSH_MAXH];
+    __shared__ int lo_s[LSH_MAXH + 1], n_s[LSH_MAXH + 1];
+    __shared__ Acc8 acc[32 * 8];                // a pass's rows (32 x 8 parts)
+    __shared__ Acc8 cacc[15 * 8];               // the coherence rows
+    __shared__ double sump[15], sumw[15];
+    __shared__ long long rix[15];
+    __shared__ int rpos[15][3];
+    __shared__ double rd[4], rw[4];
+    __shared__ long long ri[4];
+    constexpr long long NONE = 0x7fffffffffffffffLL;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int m = blockIdx.x;
+    const int ro = tid >> 3, j = tid & 7;
+    const int y = f.y_lo + m, x = f.t - 3 * y;
+    // ---- one round trip: query, weights, coherence s / im
+    if (tid < D3P) {
+        const double q = tid < D3 ? f.q3[(long)m * qstride + tid] : 0.0;
+        qs[tid] = q;
+        wsh[tid] = TAIL && tid < D3 ? f.weights[tid] : 0.0;
+        qc[tid] = tid < D3 ? (float)(q - center[tid]) : 0.f;
+    }
+    if (TAIL && tid < 15) c3_window(tid, y, x, f, rix, rpos);
+    __syncthreads();
+    // ---- the hashes, one lane each
+    if (tid < lv.L * lv.k) {
+        const float4 *p4 = reinterpret_cast<const float4 *>(lv.proj + (long)tid * LSH3_PD);
+        const float4 *q4 = reinterpret_cast<const float4 *>(qc);
+        const float4 last = p4[D3 / 4];         // {p[164], b, 0, 0}
+        float d = last.y;
+#pragma unroll 8
+        for (int i = 0; i < D3 / 4; ++i) {
+            const float4 p = p4[i], a = q4[i];
+            d = fmaf(p.x, a.x, d);
+            d = fmaf(p.y, a.y, d);
+            d = fmaf(p.z, a.z, d);
+            d = fmaf(p.w, a.w, d);
+        }
+        d = fmaf(last.x, qc[D3 - 1], d);
+        hk[tid] = lsh_mix((int)floorf(d / lv.w), tid % lv.k);
+    }
+    __syncthreads();
+    // ---- per table: the bucket range, and the exclusive prefix of the candidate counts
+    if (wv == 0) {
+        int lo = 0, cnt = 0;
+        if (lane < lv.L) {
+            unsigned int key = 0;
+            for (int i = 0; i < lv.k; ++i) key += hk[lane * lv.k + i];
+            key &= (1u << lv.bits) - 1u;
+            const int *st = lv.start + (long)lane * ((1L << lv.bits) + 1);
+            long l = st[key], h = st[key + 1];
+            if (l == h) {   // empty bucket: take the neighbouring entries of the sorted table
+                l = l >= 2 ? l - 2 : 0;
+                h = l + 4 < nrows ? l + 4 : nrows;
+            }
+            lo = (int)l;
+            cnt = (int)(h - l > LSH_CAP ? LSH_CAP : h - l);
+        }
+        int inc = cnt;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(inc, o);
+            if (lane >= o) inc += v;
+        }
+        lo_s[lane] = lo;
+        n_s[lane] = inc - cnt;                  // (lanes >= L: the total)
+        if (lane == 63) n_s[LSH_MAXH] = inc;
+    }
+    __syncthreads();
+    const int total = n_s[LSH_MAXH];
+    const int npass = total > 32 ? (total + 31) / 32 : 1;
+    // ---- the candidates, 32 rows per pass (and, with the first, the coherence rows)
+    int tb = 0;
+    auto cand = [&](int c) -> long {            // the row of candidate c (-1: none)
+        if (c >= total) return -1;
+        while (n_s[tb + 1] <= c) ++tb;
+        const int lr = lv.rows[(long)tb * lv.npad + lo_s[tb] + (c - n_s[tb])];
+        return lr < nrows ? (long)lr : -1;
+    };
+    double bd = INFINITY, bw = 0.0;
+    long long bi = NONE;
+    long r = cand(ro);
+    for (int b = 0; b < npass; ++b) {
+        const long rn = b + 1 < npass ? cand(32 * (b + 1) + ro) : -1;
+        Acc8 ta{}, ca{};
+        if (r >= 0) ta = acc8_row(f.db3 + r * D3P, j, qs, wsh);
+        if (TAIL && b == 0 && tid < 15 * 8) {
+            const long long ix = rix[ro];
+            ca = acc8_row(f.db3 + (ix >= 0 ? ix : 0) * D3P, j, qs, wsh);
+        }
+        acc[tid] = ta;
+        if (TAIL && b == 0 && tid < 15 * 8) cacc[tid] = ca;
+        __syncthreads();
+        if (j == 0 && r >= 0) {
+            const double d = acc8_sum(acc + 8 * ro, false);
+            if (d < bd || (d == bd && r < bi)) {
+                bd = d;
+                bi = r;
+                const double sq = sqrt(acc8_sum(acc + 8 * ro, true));
+                bw = sq * sq;
+            }
+        }
+        if (TAIL && b == 0 && j == 0 && tid < 15 * 8) {
+            if (rix[ro] >= 0) {
+                sump[ro] = sqrt(acc8_sum(cacc + 8 * ro, false));
+                const double sq = sqrt(acc8_sum(cacc + 8 * ro, true));
+                sumw[ro] = sq * sq;
+            } else {
+                sump[ro] = INFINITY;
+                sumw[ro] = 0.0;
+            }
+        }
+        __syncthreads();   // acc is refilled by the next pass
+        r = rn;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(bd, o), ow = __shfl_xor(bw, o);
+        const long long oi = __shfl_xor(bi, o);
+        if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; bw = ow; }
+    }
+    if (lane == 0) { rd[wv] = bd; ri[wv] = bi; rw[wv] = bw; }
+    __syncthreads();
+    double wd = rd[0], ww = rw[0];
+    long long wi = ri[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+        if (rd[w] < wd || (rd[w] == wd && ri[w] < wi)) { wd = rd[w]; wi = ri[w]; ww = rw[w]; }
+    if (wi == NONE) {   // (workgroup-uniform) no valid candidate: row 0
+        if (tid < 8) acc[tid] = acc8_row(f.db3, tid, qs, wsh);
+        __syncthreads();
+        wi = 0;
+        wd = acc8_sum(acc, false);
+        const double sq = sqrt(acc8_sum(acc, true));
+        ww = sq * sq;
+    }
+    if constexpr (TAIL) {
+        if (wv != 0) return;
+        const long src = c3_decide(f, y, x, lane, wi, ww, sump, sumw, rix, rpos);
+        if (lane < 3) f.Bp_lg[((long)y * f.W + x) * 3 + lane] = f.Ap_lg[src + lane];
+    } else {
+        if (tid == 0) {
+            if (idx) idx[m] = wi;
+            if (dist) dist[m] = wd;
+        }
+    }
+}
+
 // the replicated fp64 pyramids of a level's A side (feat3's inputs, as k_db3_build's)
 struct Src3 {
     Img3 Asm, Alg;
@@ -1428,9 +1596,18 @@ static inline size_t ws3_layout(int H, int W, long nrows, char *base, Ws3 *w, in
     return o;
 }
 
+// a level's lsh (NULL: fine): only on an unsharded level, with its centre and usable tables
+static int lsh3_level_check(const IaSynthArgs &a, const char *who) {
+    if (!a.lsh) return IA_OK;
+    IA_ARG(!a.comm, std::string(who) + ": a sharded level runs the exact matcher (comm with lsh)");
+    IA_ARG(a.center, std::string(who) + ": lsh needs center (165 doubles)");
+    return lsh3_check(a.lsh, who);
+}
+
 // one 3-channel level (all its rows, or this rank's shard): the wave loop of ia_synth_level3
 // (per wave: the query rows and split operand, the screen, the exact stage + tail; or the
-// exhaustive fp64 search; a sharded level: wave_sharded)
+// exhaustive fp64 search; an LSH level: the query rows, k_lsh3_pixel; a sharded level:
+// wave_sharded)
 struct Level3 {
     const IaSynthArgs *a = nullptr;
     Ws3 w{};
@@ -1441,6 +1618,8 @@ struct Level3 {
     int H = 0, W = 0, nw = 0, nb = 0, ntiles = 0;
     bool split = true, rot = false;   // rot: the R16c screen (a->dbr, a->rot: ia_db3_build_rot)
     bool fuse = false;                // rot with the fused tail (k_exact3<true>)
+    bool lsh = false;                 // the LSH matcher (a->lsh, a->center): k_lsh3_pixel
+    Lsh3View lv{};
     const half8 *dbr = nullptr;
     // a sharded level (a->comm): rows [row0, row0 + nrows) of N_total, one exchange per wave
     bool sharded = false, peer = false;
@@ -1451,7 +1630,11 @@ struct Level3 {
         IA_ARG(a && a->db && a->B_sm && a->B_lg && a->Bp_sm && a->Bp_lg && a->weights && a->s && a->im &&
                    a->workspace && a->H > 0 && a->W > 0,
                "ia_synth_level3: bad args");
-        IA_ARG(!a->lsh, "ia_synth_level3: 3-channel matching runs the exact matcher (lsh must be NULL)");
+        {
+            const int rc = lsh3_level_check(*a, "ia_synth_level3");
+            if (rc) return rc;
+        }
+        lsh = a->lsh != nullptr;
         const long N = (long)a->src.nAp * a->src.Ah * a->src.Aw;
         sharded = a->comm != nullptr;
         if (!sharded) {
@@ -1485,7 +1668,8 @@ struct Level3 {
                  0, 0, W, a->weights, a->kappa_factor, a->Bp_lg, a->s, a->im, a->dbg_px, a->dbg_dist};
         split = g_color16.load(std::memory_order_relaxed) != 0;
         ntiles = (int)v.ntiles;
-        rot = split && a->dbr && a->rot;
+        if (lsh) lv = lsh3_view(a->lsh, a->nrows);
+        rot = split && a->dbr && a->rot && !lsh;   // (an LSH level reads no screen operand)
         dbr = reinterpret_cast<const half8 *>(a->dbr);
         sc = Scr3{w.smin, ntiles, a->nrows, w.qn, v.meta, g_c3_stats, rot ? w.nsk : nullptr,
                   rot ? db3r_meta(const_cast<void *>(a->dbr), a->nrows) : nullptr};
@@ -1562,7 +1746,10 @@ struct Level3 {
         f.t = t;
         f.y_lo = y_lo;
         if (sharded) return wave_sharded(M, st);
-        if (fuse) {
+        if (lsh) {
+            k_query3<<<M, 256, 0, st>>>(Bsm, Blg, Bpsm, Bplg, t, y_lo, w.q3);
+            k_lsh3_pixel<true><<<M, 256, 0, st>>>(f, lv, a->center, a->nrows, D3P, nullptr, nullptr);
+        } else if (fuse) {
             // wave t's query set b (wave 0's built here, the later ones by the previous wave's
             // k_exact3<true>), wave t + 1's into set b ^ 1
             const int b = t & 1;
@@ -1718,6 +1905,21 @@ int ia_match3_batch(const double *db3, long nrows, const double *q165, int M, in
     return IA_OK;
 }
 
+int ia_lsh3_match_batch(const double *db3, long nrows, const double *center, const IaLsh *lsh,
+                        const double *q165, int M, int64_t *idx, double *dist, void *stream) {
+    IA_ARG(db3 && center && lsh && q165 && M > 0 && nrows > 0, "ia_lsh3_match_batch: bad args");
+    {
+        const int rc = lsh3_check(lsh, "ia_lsh3_match_batch");
+        if (rc) return rc;
+    }
+    Fin3 f{};
+    f.db3 = db3;
+    f.q3 = q165;
+    k_lsh3_pixel<false><<<M, 256, 0, S(stream)>>>(f, lsh3_view(lsh, nrows), center, nrows, D3, idx, dist);
+    IA_LAUNCH_CHECK("k_lsh3_pixel");
+    return IA_OK;
+}
+
 size_t ia_synth3_workspace_bytes(int H, int W, long nrows) { return ws3_layout(H, W, nrows, nullptr, nullptr); }
 
 size_t ia_synth3_shard_workspace_bytes(int H, int W, long nrows, int nranks) {
@@ -1824,6 +2026,11 @@ static int synth_levels3(const IaSynthArgs *levels, int n, int K, void *stream) 
             IA_ARG(l.Bp_sm == c.Bp_lg && l.B_hs == c.H && l.B_ws == c.W,
                    who + ": levels must be consecutive (level j's coarse B' = level j-1's B')");
         }
+    // (an lsh that cannot run is refused before anything is enqueued)
+    for (size_t i = 0; i < (size_t)n * K; ++i) {
+        const int rc = lsh3_level_check(levels[i], who.c_str());
+        if (rc) return rc;
+    }
     // a batch: every job of a level in the same shapes and forms (checked before anything is
     // enqueued; the message names the field)
     if (K > 1) {
@@ -1885,6 +2092,8 @@ int ia_synth_levels3_batch(const IaSynthArgs *levels, int n, int K, void *stream
     IA_ARG(levels && n >= 1 && n <= 64, "ia_synth_levels3_batch: bad level count");
     for (size_t i = 0; i < (size_t)n * K; ++i)   // (batches shard by job, not by rows)
         IA_ARG(!levels[i].comm, "ia_synth_levels3_batch: a batch takes no comm (sharded levels: ia_synth_levels3)");
+    for (size_t i = 0; i < (size_t)n * K; ++i)   // (for any K: the LSH matcher has no batch form)
+        IA_ARG(!levels[i].lsh, "ia_synth_levels3_batch: a batch takes no lsh (LSH levels: ia_synth_levels3)");
     return synth_levels3(levels, n, K, stream);
 }
 

@@ -427,4 +427,35 @@ int launch_lsh_match(const IaLsh *lsh, const DbSrc &src, long row0, long nrows, 
                      const double *q64, const double *center, Best *best,
                      unsigned long long *stats, hipStream_t st);
 
+// ---- the LSH definition's constants, shared by the luminance tables (ia_lsh.hip) and the
+// 165-dim ones (tables: ia_lsh.hip ia_lsh3_build; queries: ia_color3.hip k_lsh3_pixel)
+constexpr int LSH_MAXH = 64;     // L * k hashes per row (one lane each in the query)
+constexpr int LSH_CAP = 32;      // rows examined per (query, table) bucket
+// key bits: ceil(log2(nrows)) + 1, in [2, 30]
+static inline int lsh_bits(long nrows) {
+    int b = 1;
+    while (b < 29 && (1L << b) < nrows) ++b;
+    return b + 1;
+}
+__device__ __forceinline__ unsigned int lsh_mix(int h, int i) {
+    return (unsigned int)h * (0x9E3779B1u + 2u * (unsigned int)i) + 0x7F4A7C15u * (unsigned int)i;
+}
+// 165-dim rows: projection rows of LSH3_PD floats (p in 0..164, the offset b in 165, zeros);
+// the tables' rows are padded to a multiple of 256 (the colour path's own rule: it does not
+// depend on the calling thread's chunk target as db_rows_padded does)
+constexpr int LSH3_D = 165, LSH3_PD = 168;
+static inline long lsh3_rows_padded(long nrows) { return (nrows + 255) / 256 * 256; }
+// what a query reads of an ia_lsh3_build table set: rows[t][npad] (sorted by key, stable),
+// start[t][2^bits + 1] (the bucket directory) and the hash parameters
+struct Lsh3View {
+    const int *rows, *start;
+    const float *proj;
+    int L, k, bits;
+    float w;
+    long npad;
+};
+// IA_E_ARG unless lsh holds usable 165-dim tables' parameters (who: the caller's name)
+int lsh3_check(const IaLsh *lsh, const char *who);
+Lsh3View lsh3_view(const IaLsh *lsh, long nrows);
+
 }  // namespace ia

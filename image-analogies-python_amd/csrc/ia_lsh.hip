@@ -13,25 +13,16 @@
 // distance (the oracle's pairwise-8 value) of up to LSH_CAP rows per bucket, spread over
 // the wave's lanes; the lexicographic (distance, row) minimum is returned.
 // Approximate by construction: the exact matcher is the default.
+// 3-channel matching (165-dim rows) keeps the definition with D = 165: ia_lsh3_build makes the
+// same tables from the materialised fp64 rows of ia_db3_build (k_lsh3_keys, then the shared
+// sort and directory); its queries are ia_color3.hip's k_lsh3_pixel.
 #include "ia_internal.h"
 
 #include <hipcub/hipcub.hpp>
 
 namespace ia {
 
-constexpr int LSH_MAXH = 64;     // L * k hashes per row (one lane each in the query)
-constexpr int LSH_CAP = 32;      // rows examined per (query, table) bucket
-
-// key bits: ceil(log2(nrows)) + 1, in [2, 30]
-static inline int lsh_bits(long nrows) {
-    int b = 1;
-    while (b < 29 && (1L << b) < nrows) ++b;
-    return b + 1;
-}
-
-__device__ __forceinline__ unsigned int lsh_mix(int h, int i) {
-    return (unsigned int)h * (0x9E3779B1u + 2u * (unsigned int)i) + 0x7F4A7C15u * (unsigned int)i;
-}
+// (LSH_MAXH, LSH_CAP, lsh_bits, lsh_mix: ia_internal.h, shared with the 165-dim tables)
 
 // keys_in[t][r] for the local rows r of [row0, row0 + nrows): the centred fp32 values
 // fl32(a_k - c_k) gathered from the pyramids (the rows the exact matcher screens)
@@ -81,6 +72,59 @@ __global__ __launch_bounds__(256) void k_lsh_dir(const unsigned int *__restrict_
     for (long b = kp + 1; b <= kc; ++b) st[b] = (int)i;
     if (i == npad - 1)   // sentinels hold key 2^bits: nothing beyond
         for (long b = kc + 1; b <= (1L << bits); ++b) st[b] = (int)npad;
+}
+
+// ---- keys of 165-dim rows (3-channel matching: the materialised fp64 rows of ia_db3_build,
+// LSH3_PD doubles apart).  The luminance kernel's whole row per thread would spill at 165
+// floats, so a workgroup stages the projections (odd LDS stride: lanes of consecutive hashes
+// on distinct banks) and a tile of K3_ROWS centred fp32 rows (coalesced reads of the 1,344-B
+// rows) in LDS; threads then take (row, hash) pairs, each the 165-term fmaf chain in the
+// definition's order, and (row, table) pairs sum the k mixed hashes into the key.  A workgroup
+// walks tiles blockIdx.x, + gridDim.x, ...: the projections are staged once per workgroup.
+constexpr int K3_ROWS = 16, K3_PS = LSH3_PD + 1;
+__global__ __launch_bounds__(256) void k_lsh3_keys(const double *__restrict__ db3, long nrows, long npad,
+                                                   const double *__restrict__ center,
+                                                   const float *__restrict__ proj, int L, int k,
+                                                   float w, int bits, unsigned int *__restrict__ keys,
+                                                   int *__restrict__ rows) {
+    __shared__ float P[LSH_MAXH * K3_PS];          // 43,264 B
+    __shared__ float X[K3_ROWS * LSH3_PD];         // 10,752 B
+    __shared__ double cs[LSH3_PD];
+    __shared__ unsigned int hk[K3_ROWS * LSH_MAXH];
+    const int tid = threadIdx.x, nh = L * k;
+    for (int i = tid; i < nh * LSH3_PD; i += 256) {
+        const int h = i / LSH3_PD, e = i - h * LSH3_PD;
+        P[h * K3_PS + e] = proj[i];
+    }
+    for (int e = tid; e < LSH3_PD; e += 256) cs[e] = e < LSH3_D ? center[e] : 0.0;
+    const unsigned int mask = (1u << bits) - 1u;
+    for (long r0 = (long)blockIdx.x * K3_ROWS; r0 < npad; r0 += (long)gridDim.x * K3_ROWS) {
+        __syncthreads();   // cs and P staged; the previous tile's X and hk consumed
+        for (int i = tid; i < K3_ROWS * LSH3_PD; i += 256) {
+            const int rr = i / LSH3_PD, e = i - rr * LSH3_PD;
+            const long r = r0 + rr < nrows ? r0 + rr : nrows - 1;   // (sentinel rows: key unused)
+            X[i] = e < LSH3_D ? (float)(db3[r * LSH3_PD + e] - cs[e]) : 0.f;
+        }
+        __syncthreads();
+        for (int i = tid; i < K3_ROWS * nh; i += 256) {
+            const int rr = i / nh, h = i - rr * nh;
+            const float *p = P + h * K3_PS, *a = X + rr * LSH3_PD;
+            float d = p[LSH3_D];
+#pragma unroll 5
+            for (int e = 0; e < LSH3_D; ++e) d = fmaf(p[e], a[e], d);
+            hk[rr * LSH_MAXH + h] = lsh_mix((int)floorf(d / w), h % k);
+        }
+        __syncthreads();
+        for (int i = tid; i < K3_ROWS * L; i += 256) {
+            const int t = i / K3_ROWS, rr = i - t * K3_ROWS;
+            const long r = r0 + rr;
+            unsigned int key = 0;
+            for (int j = 0; j < k; ++j) key += hk[rr * LSH_MAXH + t * k + j];
+            // rows past nrows (sentinels) get the key 2^bits, beyond every bucket
+            keys[(long)t * npad + r] = r < nrows ? (key & mask) : mask + 1u;
+            rows[(long)t * npad + r] = (int)r;
+        }
+    }
 }
 
 __device__ __forceinline__ void lbest(double &bd, long long &bi, double d, long long i) {
@@ -164,8 +208,9 @@ struct LshLayout {
     size_t rows, start, keys, keys_in, rows_in, tmp, total;
 };
 static size_t sort_temp_bytes(long npad, int bits);
-static LshLayout lsh_layout(long nrows, int L) {
-    const long npad = db_rows_padded(nrows);
+// (npad: the padded row count, db_rows_padded(nrows) for the luminance tables,
+// lsh3_rows_padded(nrows) for the 165-dim ones)
+static LshLayout lsh_layout_n(long nrows, long npad, int L) {
     const int bits = lsh_bits(nrows);
     const size_t tab = align_up((size_t)L * npad * 4, 256);
     LshLayout y;
@@ -177,6 +222,47 @@ static LshLayout lsh_layout(long nrows, int L) {
     y.tmp = y.rows_in + tab;
     y.total = y.tmp + align_up(sort_temp_bytes(npad, bits), 256);
     return y;
+}
+static LshLayout lsh_layout(long nrows, int L) { return lsh_layout_n(nrows, db_rows_padded(nrows), L); }
+
+// the tables of npad padded rows from their unsorted (key, row) pairs in keys_in / rows_in: one
+// stable radix sort per table, then the bucket directory
+static int lsh_sort_tables(char *m, const LshLayout &y, long npad, int bits, int L, hipStream_t st,
+                           const char *who) {
+    int *rows = reinterpret_cast<int *>(m + y.rows);
+    int *start = reinterpret_cast<int *>(m + y.start);
+    unsigned int *keys = reinterpret_cast<unsigned int *>(m + y.keys);
+    unsigned int *keys_in = reinterpret_cast<unsigned int *>(m + y.keys_in);
+    int *rows_in = reinterpret_cast<int *>(m + y.rows_in);
+    void *tmp = m + y.tmp;
+    size_t tb = sort_temp_bytes(npad, bits);
+    IA_ARG(tb > 0, std::string(who) + ": radix-sort size query failed");
+    for (int t = 0; t < L; ++t) {
+        IA_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys_in + (long)t * npad,
+                                                  keys + (long)t * npad, rows_in + (long)t * npad,
+                                                  rows + (long)t * npad, (int)npad, 0, bits + 1,
+                                                  st));
+    }
+    k_lsh_dir<<<dim3((unsigned)((npad + 255) / 256), L), 256, 0, st>>>(keys, npad, bits, start);
+    IA_LAUNCH_CHECK("k_lsh_dir");
+    return IA_OK;
+}
+
+int lsh3_check(const IaLsh *lsh, const char *who) {
+    IA_ARG(lsh->mem && lsh->proj, std::string(who) + ": lsh without tables (mem, proj)");
+    IA_ARG((reinterpret_cast<uintptr_t>(lsh->proj) & 15) == 0,
+           std::string(who) + ": lsh proj must be 16-byte aligned");
+    IA_ARG(lsh->L >= 1 && lsh->k >= 1 && lsh->L * lsh->k <= LSH_MAXH && lsh->w > 0.f,
+           std::string(who) + ": lsh needs 1 <= L*k <= 64 and w > 0");
+    return IA_OK;
+}
+
+Lsh3View lsh3_view(const IaLsh *lsh, long nrows) {
+    const long npad = lsh3_rows_padded(nrows);
+    const LshLayout y = lsh_layout_n(nrows, npad, lsh->L);
+    const char *m = reinterpret_cast<const char *>(lsh->mem);
+    return Lsh3View{reinterpret_cast<const int *>(m + y.rows), reinterpret_cast<const int *>(m + y.start),
+                    lsh->proj, lsh->L, lsh->k, lsh_bits(nrows), lsh->w, npad};
 }
 
 int launch_lsh_match(const IaLsh *lsh, const DbSrc &src, long row0, long nrows, int M,
@@ -227,27 +313,41 @@ int ia_lsh_build(const IaSrcLevel *src, long row0, long nrows, const double *cen
     const int bits = lsh_bits(nrows);
     const LshLayout y = lsh_layout(nrows, lsh->L);
     char *m = reinterpret_cast<char *>(lsh->mem);
-    int *rows = reinterpret_cast<int *>(m + y.rows);
-    int *start = reinterpret_cast<int *>(m + y.start);
-    unsigned int *keys = reinterpret_cast<unsigned int *>(m + y.keys);
-    unsigned int *keys_in = reinterpret_cast<unsigned int *>(m + y.keys_in);
-    int *rows_in = reinterpret_cast<int *>(m + y.rows_in);
-    void *tmp = m + y.tmp;
-    size_t tb = sort_temp_bytes(npad, bits);
-    IA_ARG(tb > 0, "ia_lsh_build: radix-sort size query failed");
+    IA_ARG(sort_temp_bytes(npad, bits) > 0, "ia_lsh_build: radix-sort size query failed");
     const unsigned nb = (unsigned)((npad + 255) / 256);
     k_lsh_keys<<<nb, 256, 0, st>>>(make_dbsrc(*src), row0, nrows, npad, center, lsh->proj,
-                                   lsh->L, lsh->k, lsh->w, bits, keys_in, rows_in);
+                                   lsh->L, lsh->k, lsh->w, bits,
+                                   reinterpret_cast<unsigned int *>(m + y.keys_in),
+                                   reinterpret_cast<int *>(m + y.rows_in));
     IA_LAUNCH_CHECK("k_lsh_keys");
-    for (int t = 0; t < lsh->L; ++t) {
-        IA_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys_in + (long)t * npad,
-                                                  keys + (long)t * npad, rows_in + (long)t * npad,
-                                                  rows + (long)t * npad, (int)npad, 0, bits + 1,
-                                                  st));
+    return lsh_sort_tables(m, y, npad, bits, lsh->L, st, "ia_lsh_build");
+}
+
+size_t ia_lsh3_bytes(long nrows, int L) {
+    if (nrows <= 0 || L <= 0) return 0;
+    return lsh_layout_n(nrows, lsh3_rows_padded(nrows), L).total;
+}
+
+int ia_lsh3_build(const double *db3, long nrows, const double *center, const IaLsh *lsh, void *stream) {
+    IA_ARG(db3 && center && lsh && nrows > 0, "ia_lsh3_build: bad args");
+    {
+        const int rc = lsh3_check(lsh, "ia_lsh3_build");
+        if (rc) return rc;
     }
-    k_lsh_dir<<<dim3(nb, lsh->L), 256, 0, st>>>(keys, npad, bits, start);
-    IA_LAUNCH_CHECK("k_lsh_dir");
-    return IA_OK;
+    IA_ARG(nrows < (1L << 31) - 256, "ia_lsh3_build: too many rows");
+    hipStream_t st = S(stream);
+    const long npad = lsh3_rows_padded(nrows);
+    const int bits = lsh_bits(nrows);
+    const LshLayout y = lsh_layout_n(nrows, npad, lsh->L);
+    char *m = reinterpret_cast<char *>(lsh->mem);
+    IA_ARG(sort_temp_bytes(npad, bits) > 0, "ia_lsh3_build: radix-sort size query failed");
+    // (at most 1,024 workgroups walk the tiles: the projections are staged once per workgroup)
+    const long tiles = npad / K3_ROWS;
+    k_lsh3_keys<<<(unsigned)(tiles < 1024 ? tiles : 1024), 256, 0, st>>>(
+        db3, nrows, npad, center, lsh->proj, lsh->L, lsh->k, lsh->w, bits,
+        reinterpret_cast<unsigned int *>(m + y.keys_in), reinterpret_cast<int *>(m + y.rows_in));
+    IA_LAUNCH_CHECK("k_lsh3_keys");
+    return lsh_sort_tables(m, y, npad, bits, lsh->L, st, "ia_lsh3_build");
 }
 
 }  // extern "C"

@@ -280,7 +280,7 @@ def level3_resources(args):
 
 
 def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, levels=None,
-                    debug=False, pipeline=None, comm=None, rank=0, nranks=1):
+                    debug=False, pipeline=None, comm=None, rank=0, nranks=1, lsh=None):
     """3-channel synthesis (num_ch = 3: convert=False on colour images, 165-dim rows): per
     level the materialised fp64 database (ia_db3_build), and by default (IA_DB_ROT) its
     rotated split-f16 form (R16c, DESIGN.md §4e: ia_db3_build_rot under ONE rotation for all
@@ -296,7 +296,12 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
     k_peer_finish3 collects every rank's and finishes the pixel) and the others
     run replicated; pipelined sharded levels need one exchange each, and with nranks > 1 on the
     device-side exchange sharded_schedule decides from ia_level3_resources whether they may
-    overlap.  Same return value as synthesize_dev."""
+    overlap.  lsh: None, or LevelIndex3.build_lsh arguments: every level then runs the
+    approximate LSH matcher (algorithms.lsh3_tables per level; a wave is k_query3 and
+    k_lsh3_pixel), the rotated DB, which nothing reads then, is not built, and the levels run
+    unsharded (a comm is refused).  Same return value as synthesize_dev."""
+    if lsh is not None and comm is not None:
+        raise NotImplementedError('sharded 3-channel levels run the exact matcher')
     lib = _ia.lib()
     st = _ia.stream()
     weights = weights if torch.is_tensor(weights) else _ia.to_dev(weights)
@@ -324,7 +329,8 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
     # levels' rows have nearly the same principal directions, and any orthonormal basis keeps
     # the matcher exact); 0: each level its own
     shared = None
-    if _ia.db_rot_enabled() and todo and os.environ.get('IA_ROT3_SHARED', '1') != '0':
+    use_rot = _ia.db_rot_enabled() and lsh is None
+    if use_rot and todo and os.environ.get('IA_ROT3_SHARED', '1') != '0':
         # (of this rank's rows of it, where that level is sharded: the ranks need not agree)
         db3f, (_, nf) = built[todo[-1]][6:8]
         shared = algorithms.rot3_rotation(db3f, nf)
@@ -334,10 +340,16 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
         rot = dbr = None
         if shared is not None:
             rot, dbr = shared, algorithms.rot3_apply(db3, nrows, shared)
-        elif _ia.db_rot_enabled():
+        elif use_rot:
             rot, dbr = algorithms.rot3_build(db3, nrows)
-        prepared.append((level, rot, dbr) + _level3_args(built[level], rot, dbr, B_pyr, Bp_pyr, level, max_levels,
-                                                         k, weights, debug, level_comm(level)))
+        a, res, bufs = _level3_args(built[level], rot, dbr, B_pyr, Bp_pyr, level, max_levels,
+                                    k, weights, debug, level_comm(level))
+        if lsh is not None:
+            A_lg, Ap_lg = built[level][1], built[level][3]
+            tabs = algorithms.lsh3_tables(A_lg, Ap_lg, db3, nrows, **lsh)
+            a.lsh, a.center = ctypes.pointer(tabs[0]), _ia.ptr(tabs[1]).value
+            bufs = bufs + (tabs,)
+        prepared.append((level, rot, dbr, a, res, bufs))
     if peer_rule:
         # k_peer_finish3's waiting workgroups must leave room for the screens
         res = [level3_resources(p[3]) for p in prepared if p[0] in sharded]
@@ -348,14 +360,14 @@ def synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights, l
         if os.environ.get('IA_VERBOSE'):
             print('[ia] sharded colour levels %s: kernels %s, pipelined %s' % (sharded, res, pipeline),
                   file=sys.stderr, flush=True)
-    for level, rot, dbr, a, (s, im, dbg), (B_sm, B_lg, ws) in prepared:
+    for level, rot, dbr, a, (s, im, dbg), bufs in prepared:    # (bufs: B_sm, B_lg, ws[, LSH tables])
         A_sm, A_lg, Ap_sm, Ap_lg, _, _, db3, _ = built[level]
-        done.append((a, (A_sm, A_lg, Ap_sm, Ap_lg, B_sm, B_lg, db3, ws, rot, dbr)))
+        done.append((a, (A_sm, A_lg, Ap_sm, Ap_lg, db3, rot, dbr) + bufs))
         if not pipeline:
             _ia.check(lib.ia_synth_level3(ctypes.byref(a), st), 'ia_synth_level3')
         else:
             args.append(a)
-            keep.append((A_sm, A_lg, Ap_sm, Ap_lg, B_sm, B_lg, db3, ws, rot, dbr))
+            keep.append((A_sm, A_lg, Ap_sm, Ap_lg, db3, rot, dbr) + bufs)
         out[level] = (s, im) if dbg is None else (s, im, dbg)
     if args:
         # consecutive runs of levels go through one pipelined call each
@@ -431,7 +443,8 @@ def synthesize_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights,
                    pipeline=None, debug=False, check=True):
     """Synthesise levels 1..max_levels-1 (image_analogies.py:119-220) from device
     pyramids.  Bp_pyr (list of device tensors) is updated in place.  lsh: None (exact
-    matcher) or LevelIndex.build_lsh arguments (approximate matcher).  comm: one
+    matcher) or LevelIndex.build_lsh arguments (approximate matcher; 3-channel pyramids take
+    it too, with comm None: NotImplementedError otherwise).  comm: one
     communicator, or a list (one per sharded level, needed when sharded levels run
     pipelined).  pipeline: run the levels concurrently (ia_synth_levels; default
     pipeline_default()), else one after the other.  check: synchronise at the end and raise
@@ -442,11 +455,13 @@ def synthesize_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights,
     a later pipelined call of the same thread then waits for it to end before it enqueues
     (IA_PIPE_DRAIN).  Returns {level: (s, im[, debug])} device tensors."""
     if B_pyr[-1].dim() == 3:     # 3-channel matching (num_ch = 3)
-        if lsh is not None:
-            raise NotImplementedError('3-channel matching runs the exact matcher')
+        if lsh is not None and comm is not None:   # (before any device call, lsh not looked into)
+            raise NotImplementedError('sharded 3-channel levels run the exact matcher: '
+                                      'the LSH matcher runs on one GPU')
         return synthesize3_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights,
                                levels=levels, debug=debug,
-                               pipeline=False if eager else pipeline, comm=comm, rank=rank, nranks=nranks)
+                               pipeline=False if eager else pipeline, comm=comm, rank=rank, nranks=nranks,
+                               lsh=lsh)
     w = weights if torch.is_tensor(weights) else _ia.to_dev(weights)
     if pipeline is None:
         pipeline = pipeline_default() and not eager
@@ -657,8 +672,6 @@ def setup_dev(A_orig, Ap_orig_list, B_orig, c):
     if not c.convert and np.ndim(A_orig) == 3:
         if c.remap_lum:
             raise ValueError('remap_lum requires convert (config.py:11-12)')
-        if getattr(c, 'matcher', 'brute') != 'brute':
-            raise NotImplementedError('3-channel matching runs with the exact matcher only')
     dev = _ia.require_device()
     for Ap in Ap_orig_list:
         assert A_orig.shape == Ap.shape

@@ -245,7 +245,7 @@ int ia_db_build_rotk(const IaSrcLevel *src, long row0, long nrows, const double 
  *   ia_db3_bytes) of rows [row0, row0 + nrows).
  * ia_level_features3_f64: compute_feature_array (algorithms.py:11-47) of one level pair,
  *   h*w x 102 (full) or x 63 (half).
- * ia_synth_level3: one level with the exact matcher (the split-f16 MFMA screen
+ * ia_synth_level3: one level, by default with the exact matcher (the split-f16 MFMA screen
  *   k_screen3 and an exact fp64 rescore of its candidate tiles in the oracle's order;
  *   IA_COLOR16=0: exhaustive fp64 search of the materialised rows), the coherence / kappa
  *   tail and the 3-channel B' update.  comm NULL: a->db = ia_db3_build output over all rows
@@ -258,6 +258,10 @@ int ia_db_build_rotk(const IaSrcLevel *src, long row0, long nrows, const double 
  *   the ranks and finishes the pixel from the replicated pyramids: every rank ends with the
  *   same B', s, im, bit-identical to the unsharded run.  IA_E_ARG for a sharded level with lsh,
  *   with IA_COLOR16=0, or with N_total >= 2^32.
+ *   lsh set (an unsharded level only): the approximate matcher over ia_lsh3_build's tables of
+ *   the same rows, with center = its 165 doubles (NULL: IA_E_ARG); a wave is then the query
+ *   rows (k_query3) and k_lsh3_pixel (hashes, bucket candidates rescored in fp64, tail); dbr,
+ *   rot and the screen operand of db are not read.
  * ia_synth_levels3: n consecutive 3-channel levels at once, pipelined as ia_synth_levels
  *   (one stream per level, wave t of level j behind the waves of level j-1 its coarse
  *   windows read); the same results as n ia_synth_level3 calls in order.  Sharded levels need
@@ -280,6 +284,20 @@ int ia_match3_batch(const double *db3, long nrows, const double *q165, int M, in
 int ia_coherence_pick3(const double *rows, int n, const double *q, int32_t *out, void *stream);
 int ia_wdist3_batch(const double *a, const double *q, const double *w, int n, double *out,
                     void *stream);
+/* the approximate matcher for 165-dim rows (config matcher='lsh' with convert=False): the
+ * definition of ia_lsh_build with D = 165.  IaLsh.proj is L*k rows of 168 floats on device, 16-
+ * byte aligned (p in elements 0..164, b in element 165, zeros after); the centred value is
+ * fl32(a_k - center[k]) for center = 165 doubles on device; h = floorf(d / w) with d from b
+ * through fmaf(p[e], a'[e], d), e = 0..164.  ia_lsh3_build fills mem (ia_lsh3_bytes(nrows, L)
+ * bytes) from the fp64 rows of an ia_db3_build buffer (rows padded to a multiple of 256).
+ * ia_lsh3_match_batch: M queries (M x 165) -> the lexicographic (distance, row) minimum over
+ * the first 32 rows of each table's bucket (an empty bucket: the 4 sorted entries around its
+ * position), the distance numpy's pairwise sum as ia_match3_batch's.  1 <= L*k <= 64, w > 0. */
+size_t ia_lsh3_bytes(long nrows, int L);
+int ia_lsh3_build(const double *db3, long nrows, const double *center, const IaLsh *lsh,
+                  void *stream);
+int ia_lsh3_match_batch(const double *db3, long nrows, const double *center, const IaLsh *lsh,
+                        const double *q165, int M, int64_t *idx, double *dist, void *stream);
 
 /* ---- a12-a15: image_analogies.py:130-220 — synthesize one pyramid level on device,
  * skewed wavefront t = x + 3y (exactly the scanline semantics).
@@ -302,7 +320,8 @@ typedef struct {
     int32_t *s, *im;
     void *workspace;
     void *comm;
-    const IaLsh *lsh;   /* NULL: exact matcher; else LSH tables of this shard's rows */
+    const IaLsh *lsh;   /* NULL: exact matcher; else LSH tables of this shard's rows (a 3-channel
+                           level: ia_lsh3_build's, unsharded only, center = 165 doubles) */
     /* IA_SYNTH_EAGER: never capture the wave loop into a HIP graph.  Capture is off by
      * default (a graph's instantiation costs more than it saves on every c4 level); the
      * environment variable IA_GRAPH=1 captures levels of <= 2^18 rows on one GPU, =2 every

@@ -15,6 +15,15 @@ usage: python tools/colour_bench.py [H W] [steps] [jobs]   (default 180 117 (c1 
        rows, the screen of the shard's tiles, k_exact3p, k_peer_finish3) without another rank's
        latency.  B' is the shard's own: timing only.  Per G: ms per level (levels one at a time,
        the median of `steps`) and ms per pipelined step
+       python tools/colour_bench.py H W steps --lsh T,H,W [T,H,W ...] [--b BH BW] [--levels N]
+       the colour LSH matcher (c.matcher = 'lsh': tables T, hashes H, width W each) against the
+       colour exact matcher on the same images (A, A' of H x W; B of BH x BW, default H x W;
+       N: the cap on pyramid halvings, with which a larger A keeps its finest level), in
+       one call: per setting both warmed up, then `steps` pairs of whole syntheses, exact and LSH
+       alternating (medians; px/s of each and exact / LSH time), and the quality of the LSH
+       run's finest level on 4,096 sampled interior pixels: the share of LSH picks equal to the
+       exact 1-NN of the same query, and the mean distance |a - q| of the LSH picks over that of
+       the exact ones
        COLOUR_PIPE=0: the colour levels one at a time (default: pipelined, ia_synth_levels3)
        COLOUR_ONLY=1: the 3-channel run alone (kernel traces of it)
 Also reports the colour exact stage's candidate tiles per query (ia_diag_color16_stats) and a
@@ -140,9 +149,87 @@ def shards_main(H, W, steps, gs):
     print(json.dumps(out))
 
 
+def lsh_main(H, W, steps, settings, BH, BW, levels=None, nq=4096):
+    """Colour LSH against the colour exact matcher on the same images (A, A' of H x W, B of
+    BH x BW), per LSH setting (tables, hashes, width): after a warm-up of both, `steps` pairs of
+    whole syntheses, exact then LSH, alternating; the medians.  levels: the cap on pyramid
+    halvings (config.levels; with it a larger A keeps its finest level against a smaller B)."""
+    import algorithms
+    from scipy.ndimage import gaussian_filter
+    dev = 'cuda:0'
+    A = np.dstack([bench.smooth_noise(7 + 17 * c, (H, W)) for c in range(3)])
+    Ap = np.dstack([gaussian_filter(A[..., c], 1.5) for c in range(3)])
+    B = np.dstack([bench.smooth_noise(8 + 17 * c, (BH, BW)) for c in range(3)])
+    a, ap, b = (torch.as_tensor(x).to(dev) for x in (A, Ap, B))
+    w = torch.as_tensor(cfg.compute_weights(3, 5, 12, 3)).to(dev)
+    A_pyr, Ap_pyr, B_pyr = (ip.gaussian_pyramid_dev(x, cfg.n_sm, levels) for x in (a, ap, b))
+    L = min(len(A_pyr), len(B_pyr))
+    init = [torch.as_tensor(x).to(dev)
+            for x in ip.initialize_Bp([np.empty(tuple(p.shape)) for p in B_pyr], True, 9)]
+    Bp = [x.clone() for x in init]
+    pixels = sum(int(p.shape[0] * p.shape[1]) for p in B_pyr[1:L])
+    lv = L - 1
+    out = {'A_size': [H, W], 'B_size': [BH, BW], 'level_cap': levels, 'levels': L - 1, 'pixels': pixels,
+           'finest_rows': int(Ap_pyr[lv].shape[0] * Ap_pyr[lv].shape[1]), 'steps': steps, 'lsh': []}
+
+    def step(lsh):
+        pa, pap, pb = (ip.gaussian_pyramid_dev(x, cfg.n_sm, levels) for x in (a, ap, b))
+        for d, s in zip(Bp, init):
+            d.copy_(s)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ia.synthesize_dev(pa, [pap], pb, Bp, L, 0.5, w, lsh=lsh)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for T, K, width in settings:
+        lsh = dict(tables=T, hashes=K, width=width, seed=0)
+        step(None)
+        step(lsh)
+        te, tl = [], []
+        for _ in range(steps):
+            te.append(step(None))
+            tl.append(step(lsh))
+        # quality on the finest level of the LSH run just made: nq interior pixels (their causal
+        # B' windows hold final values, so the rows below are the synthesis's own queries), the
+        # LSH pick of the same tables against the exact 1-NN
+        index = algorithms.LevelIndex3(A_pyr[lv - 1], A_pyr[lv], Ap_pyr[lv - 1][None], Ap_pyr[lv][None])
+        index.build_lsh(**lsh)
+        Hq, Wq = B_pyr[lv].shape[:2]
+        Q = torch.cat([algorithms.level_features3_dev(B_pyr[lv - 1], B_pyr[lv], True),
+                       algorithms.level_features3_dev(Bp[lv - 1], Bp[lv], False)], 1)
+        rs = np.random.RandomState(1)
+        ys, xs = rs.randint(2, Hq, nq), rs.randint(2, Wq, nq)
+        Qs = Q[torch.as_tensor(ys * Wq + xs).to(dev)]
+        li, ld = index.match(Qs)
+        ei, ed = index.match(Qs, exact=True)
+        me, ml = float(np.median(te)), float(np.median(tl))
+        out['lsh'].append({'tables': T, 'hashes': K, 'width': width,
+                           'exact_ms': round(me, 3), 'lsh_ms': round(ml, 3),
+                           'exact_px_per_s': pixels / (me * 1e-3), 'lsh_px_per_s': pixels / (ml * 1e-3),
+                           'speedup': me / ml,
+                           'exact_ms_steps': [round(t, 3) for t in te], 'lsh_ms_steps': [round(t, 3) for t in tl],
+                           'exact_pick_share': float((li == ei).double().mean()),
+                           'dist_ratio': float(ld.sqrt().mean() / ed.sqrt().mean()),
+                           'sampled_queries': nq})
+        del index, Q, Qs
+    print(json.dumps(out))
+
+
 def main():
     H, W = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (180, 117)
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    if '--lsh' in sys.argv:
+        rest = sys.argv[sys.argv.index('--lsh') + 1:]
+        BH, BW, levels = H, W, None
+        if '--levels' in rest:
+            levels = int(rest[rest.index('--levels') + 1])
+            del rest[rest.index('--levels'):rest.index('--levels') + 2]
+        if '--b' in rest:
+            BH, BW = int(rest[rest.index('--b') + 1]), int(rest[rest.index('--b') + 2])
+            rest = rest[:rest.index('--b')]
+        settings = [(int(t), int(k), float(wd)) for t, k, wd in (s.split(',') for s in rest)]
+        return lsh_main(H, W, steps, settings or [(16, 4, 1.0)], BH, BW, levels)
     if '--shards' in sys.argv:
         return shards_main(H, W, steps, [int(g) for g in sys.argv[sys.argv.index('--shards') + 1:]] or [1, 2, 4, 8])
     if len(sys.argv) > 4 and int(sys.argv[4]) > 1:
