@@ -813,6 +813,12 @@ static inline dim3 screen3r_grid(int ntiles, int M, int &tpw, int K = 1) {
     tpw = (int)std::max(1L, ((long)ntiles * QG * K + 4L * 512 - 1) / (4L * 512));
     return dim3((unsigned)((ntiles + 4 * tpw - 1) / (4 * tpw)), (unsigned)QG, (unsigned)K);
 }
+// the grid of k_screen3rs: y covers the longest group's query groups (qg_max), z the G groups;
+// tpw from the launch's qg_total (row tile, query group) pairs per row tile, the same aim
+static inline dim3 screen3rs_grid(int ntiles, int qg_total, int qg_max, int G, int &tpw) {
+    tpw = (int)std::max(1L, ((long)ntiles * qg_total + 4L * 512 - 1) / (4L * 512));
+    return dim3((unsigned)((ntiles + 4 * tpw - 1) / (4 * tpw)), (unsigned)qg_max, (unsigned)G);
+}
 
 // eps of the R16c screen: u (850 A|q'| + 60 A^2) + 2^-9 1.01 A_skip |kappa_skip|
 __device__ __forceinline__ double r3_eps(double A, double nqq, double askip, double nsk) {
@@ -1065,7 +1071,11 @@ __global__ __launch_bounds__(256) void k_exact3(Fin3 f, Scr3 sc, Nx3 nx) {
 // dimension (query, exact: y; screen: z, y being its query group), and job k's pointers and
 // scalars come from entry k of a device job table (one per level, in job 0's workspace).  The
 // wave's scalars stay launch arguments.  Query sets alternate by wave parity on the fused
-// path (set 0 otherwise).  Nothing is shared between jobs.
+// path (set 0 otherwise).  Jobs may pass the same database (db, dbr, rot, src: a DB group, the
+// multi_script batch's runs of one A / A' pair); no wave kernel writes into those buffers or
+// their Col16Meta / Rot3Meta (the counters are g_c3_stats), and everything written stays per
+// job.  When some do (G groups < K), the screen is k_screen3rs: one pass over a group's row
+// tiles for its jobs' query tiles together; otherwise k_screen3rb.
 constexpr int C3_CTL_ERR = 2;      // the error word's index in ctl
 struct C3Job {
     Fin3 f;                        // t, y_lo: the launch's; q3: q3[parity]
@@ -1075,6 +1085,11 @@ struct C3Job {
     float *smin;
     double *q3[2], *qn[2], *nsk[2];
     half8 *q16[2];
+    // the batch's DB groups (jobs passing one dbr, ia_batch3_groups), read by k_screen3rs; these
+    // belong to the table's entry i, not to job i: the i-th job in group order, and group i's
+    // first position in that order, job count and rotated DB
+    int sjob, gfirst, gcount;
+    const half8 *gdbr;
 };
 __global__ __launch_bounds__(256) void k_query3rb(const C3Job *__restrict__ jobs, int t, int y_lo, int M) {
     const C3Job &J = jobs[blockIdx.y];
@@ -1086,6 +1101,91 @@ __global__ __launch_bounds__(256, 2) void k_screen3rb(const C3Job *__restrict__ 
                                                       int tpw, int parity) {
     const C3Job &J = jobs[blockIdx.z];
     screen3r_body(J.dbr, ntiles, J.q16[parity], M, tpw, J.smin);
+}
+// The screen of a batch whose jobs share databases (G groups < K jobs): block (x, y, group z)
+// stages up to S3R_QG consecutive entries of the group's list of n_g QT query tiles (entry e: tile
+// e % QT of the group's job e / QT, each from its own job's q16) and walks the group's row
+// tiles once for all of them, as screen3r_body does for one job's tiles (its row-tile loop,
+// kept as a copy: a body shared with k_screen3r / k_screen3rb changes their instructions);
+// every entry's minima go to its own job's smin.  It waits for nothing.
+// entries per workgroup of a list of ne: its ceil(ne / S3R_QG) query groups, evenly filled
+__host__ __device__ constexpr int s3rs_per(int ne) {
+    return (ne + (ne + S3R_QG - 1) / S3R_QG - 1) / ((ne + S3R_QG - 1) / S3R_QG);
+}
+static_assert(s3rs_per(1) == 1 && s3rs_per(7) == 7 && s3rs_per(8) == 4 && s3rs_per(15) == 5 && s3rs_per(28) == 7,
+              "k_screen3rs: query groups");
+__global__ __launch_bounds__(256, 2) void k_screen3rs(const C3Job *__restrict__ jobs, int ntiles, int M,
+                                                      int tpw, int parity) {
+    __shared__ half8 qsh[S3R_QG * R3_TILE];
+    __shared__ gptr<const half8> src_sh[S3R_QG];   // per staged entry: its query tile,
+    __shared__ gptr<float> smin_sh[S3R_QG];        // its job's minima (gptr: global accesses)
+    __shared__ int q0_sh[S3R_QG];             // and its first query
+    const C3Job &G = jobs[blockIdx.z];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int QT = (M + 31) / 32;
+    // the list's ceil(ne / S3R_QG) query groups in equal parts (8 entries: 4 + 4, not 7 + 1: the
+    // launch is as long as its longest workgroup)
+    const int ne = G.gcount * QT, per = s3rs_per(ne), e0 = blockIdx.y * per;
+    if (e0 >= ne) return;   // (the whole workgroup, before any barrier: a smaller group's list ends here)
+    const int nq = ne - e0 < per ? ne - e0 : per;
+    if (threadIdx.x < nq) {
+        const int e = e0 + threadIdx.x, jb = e / QT, qt = e - jb * QT;
+        const C3Job &J = jobs[jobs[G.gfirst + jb].sjob];
+        src_sh[threadIdx.x] = J.q16[parity] + (long)qt * R3_TILE;
+        smin_sh[threadIdx.x] = J.smin;
+        q0_sh[threadIdx.x] = qt * 32;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nq * R3_TILE; i += 256) {
+        const int j = i / R3_TILE;
+        qsh[i] = src_sh[j].p[i - j * R3_TILE];
+    }
+    __syncthreads();
+    const gptr<const half8> db16g = G.gdbr;
+    const auto *__restrict__ db16 = db16g.p;
+    const floatx16 zero = {};
+    int t = blockIdx.x * tpw * 4 + wv;
+    if (t >= ntiles) return;   // (after the last barrier)
+    half8 a[R3_MFMA], n[R3_MFMA];
+#pragma unroll
+    for (int c = 0; c < R3_MFMA; ++c) a[c] = db16[(long)t * R3_TILE + c * 64 + lane];
+    for (int it = 0; it < tpw; ++it, t += 4) {
+        const int tn = t + 4;
+        const bool more = it + 1 < tpw && tn < ntiles;
+        if (more)
+#pragma unroll
+            for (int c = 0; c < R3_MFMA; ++c) n[c] = db16[(long)tn * R3_TILE + c * 64 + lane];
+        for (int j = 0; j < nq; j += 2) {
+            const int j1 = j + 1 < nq ? j + 1 : j;
+            const half8 *qb0 = qsh + j * R3_TILE + lane, *qb1 = qsh + j1 * R3_TILE + lane;
+            half8 b0[R3_MFMA], b1[R3_MFMA];
+#pragma unroll
+            for (int c = 0; c < R3_MFMA; ++c) {
+                b0[c] = qb0[c * 64];
+                b1[c] = qb1[c * 64];
+            }
+            floatx16 acc0 = zero, acc1 = zero;
+#pragma unroll
+            for (int c = 0; c < R3_MFMA; ++c) {
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[c], b0[c], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[c], b1[c], acc1, 0, 0, 0);
+            }
+            float mn0 = acc0[0], mn1 = acc1[0];
+#pragma unroll
+            for (int i = 1; i < 16; ++i) {
+                mn0 = fminf(mn0, acc0[i]);
+                mn1 = fminf(mn1, acc1[i]);
+            }
+            mn0 = fminf(mn0, __shfl_xor(mn0, 32));
+            mn1 = fminf(mn1, __shfl_xor(mn1, 32));
+            const int q0 = q0_sh[j] + lane, q1 = q0_sh[j1] + lane;
+            if (lane < 32 && q0 < M) smin_sh[j].p[(long)q0 * c3_stride(ntiles) + t] = mn0;
+            if (lane < 32 && j1 != j && q1 < M) smin_sh[j1].p[(long)q1 * c3_stride(ntiles) + t] = mn1;
+        }
+        if (!more) break;
+#pragma unroll
+        for (int c = 0; c < R3_MFMA; ++c) a[c] = n[c];
+    }
 }
 template <bool FUSE>
 __global__ __launch_bounds__(256) void k_exact3b(const C3Job *__restrict__ jobs, int t, int y_lo, int M,
@@ -1534,6 +1634,22 @@ static inline int match3_blocks(long nrows) { return (int)((nrows + M3_ROWS - 1)
 // fp64 search (k_match3)
 static std::atomic<int> g_color16{env_int("IA_COLOR16", 1)};
 static unsigned long long *g_c3_stats = nullptr;   // diagnostic counters (ia_diag_color16_stats)
+// IA_C3_SHARED_SCREEN (ia_diag_set_c3_shared_screen): 1 a batch whose jobs share databases
+// screens each DB group in one k_screen3rs pass, 0 every job through k_screen3rb (same minima)
+static std::atomic<int> g_c3_shared_screen{env_int("IA_C3_SHARED_SCREEN", 1)};
+
+// the DB groups of one level's K jobs (ia_batch3_groups): jobs passing the same non-null dbr
+// form a group, numbered in order of first appearance; returns their number
+static int batch3_groups(const IaSynthArgs *jobs, int K, int *group_of_job) {
+    int G = 0, first[IA_BATCH_MAX];
+    for (int k = 0; k < K; ++k) {
+        int g = 0;
+        while (g < G && !(jobs[k].dbr && jobs[first[g]].dbr == jobs[k].dbr)) ++g;
+        if (g == G) first[G++] = k;
+        group_of_job[k] = g;
+    }
+    return G;
+}
 
 // the synthesis workspace: q3 | partials (fp64 search) | q16 | qn | tile minima, and for
 // the fused R16c tail (k_exact3<true>) the odd waves' query set, the control words and the
@@ -1714,24 +1830,60 @@ struct Level3 {
         }
         pinned[0] = job_entry();
         for (int k = 1; k < K; ++k) pinned[k] = part[k - 1].job_entry();
+        // the DB groups (the caller has checked that jobs of one dbr agree in db, rot, nrows and
+        // src): the jobs in group order and each group's range of that order, in the table too
+        int grp[IA_BATCH_MAX];
+        const int G = batch3_groups(args, K, grp);
+        gcount.assign(G, 0);
+        for (int k = 0; k < K; ++k) ++gcount[grp[k]];
+        for (int g = 0, pos = 0; g < G; pos += gcount[g++]) {
+            pinned[g].gfirst = pos;
+            pinned[g].gcount = gcount[g];
+            int i = pos;
+            for (int k = 0; k < K; ++k)
+                if (grp[k] == g) {
+                    if (i == pos) pinned[g].gdbr = pinned[k].dbr;
+                    pinned[i++].sjob = k;
+                }
+        }
+        shared_screen = G < K && g_c3_shared_screen.load(std::memory_order_relaxed) != 0;
         IA_HIP(hipMemcpyAsync(w.jtab, pinned, (size_t)K * sizeof(C3Job), hipMemcpyHostToDevice, st));
         return IA_OK;
+    }
+    // a batch's DB groups: jobs per group (G = gcount.size()); shared_screen: some jobs share a
+    // database and the wave's screen is k_screen3rs (else k_screen3rb, every job for itself)
+    std::vector<int> gcount;
+    bool shared_screen = false;
+    void screen_batch(int M, int parity, hipStream_t st) {
+        int tpw;
+        if (!shared_screen) {
+            const dim3 grid = screen3r_grid(ntiles, M, tpw, K);
+            k_screen3rb<<<grid, 256, 0, st>>>(w.jtab, ntiles, M, tpw, parity);
+            return;
+        }
+        const int QT = (M + 31) / 32;
+        int total = 0, most = 0;
+        for (int n : gcount) {
+            const int qg = (n * QT + S3R_QG - 1) / S3R_QG;
+            total += qg;
+            most = std::max(most, qg);
+        }
+        const dim3 grid = screen3rs_grid(ntiles, total, most, (int)gcount.size(), tpw);
+        k_screen3rs<<<grid, 256, 0, st>>>(w.jtab, ntiles, M, tpw, parity);
     }
     // wave t of a batch: the single job's launches with the job as a grid dimension
     int wave_batch(int t, int y_lo, int M, hipStream_t st) {
         const int QT = (M + 31) / 32;
-        int tpw;
-        const dim3 grid = screen3r_grid(ntiles, M, tpw, K);
         if (fuse) {
             if (t == 0) k_query3rb<<<dim3(QT * 32, K), 256, 0, st>>>(w.jtab, t, y_lo, M);
-            k_screen3rb<<<grid, 256, 0, st>>>(w.jtab, ntiles, M, tpw, t & 1);
+            screen_batch(M, t & 1, st);
             int y_lo_n = 0, M_n = 0;
             if (t + 1 < nw) wave_rows(H, W, t + 1, y_lo_n, M_n);
             const int R = std::max(M, M_n > 0 ? y_lo_n + M_n - y_lo : 0);
             k_exact3b<true><<<dim3(R, K), 256, 0, st>>>(w.jtab, t, y_lo, M, y_lo_n, M_n);
         } else {
             k_query3rb<<<dim3(QT * 32, K), 256, 0, st>>>(w.jtab, t, y_lo, M);
-            k_screen3rb<<<grid, 256, 0, st>>>(w.jtab, ntiles, M, tpw, 0);
+            screen_batch(M, 0, st);
             k_exact3b<false><<<dim3(M, K), 256, 0, st>>>(w.jtab, t, y_lo, M, 0, 0);
         }
         IA_LAUNCH_CHECK("ia_synth_levels3_batch wave");
@@ -2045,6 +2197,17 @@ static int synth_levels3(const IaSynthArgs *levels, int n, int K, void *stream) 
                 IA_SAME(src.Ah); IA_SAME(src.Aw); IA_SAME(src.A_hs); IA_SAME(src.A_ws); IA_SAME(src.nAp);
                 IA_SAME(nrows);
 #undef IA_SAME
+                // jobs passing one rotated DB are one DB group (ia_batch3_groups): it stands for
+                // one database, so everything read with it is the same memory too
+                for (int p = 0; p < k && b.dbr; ++p) {
+                    const IaSynthArgs &c = levels[(size_t)j * K + p];
+                    if (c.dbr != b.dbr) continue;
+#define IA_SAME(field) IA_ARG(b.field == c.field, who + ": jobs sharing a dbr differ in " #field)
+                    IA_SAME(db); IA_SAME(rot); IA_SAME(nrows);
+                    IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg);
+#undef IA_SAME
+                    break;   // (p agrees with the group's earlier jobs already)
+                }
                 IA_ARG(!b.dbg_px == !a.dbg_px && !b.dbg_dist == !a.dbg_dist,
                        who + ": the jobs of a batch differ in having debug outputs (dbg_px, dbg_dist)");
                 IA_ARG(!b.dbr == !a.dbr && !b.rot == !a.rot,
@@ -2095,6 +2258,12 @@ int ia_synth_levels3_batch(const IaSynthArgs *levels, int n, int K, void *stream
     for (size_t i = 0; i < (size_t)n * K; ++i)   // (for any K: the LSH matcher has no batch form)
         IA_ARG(!levels[i].lsh, "ia_synth_levels3_batch: a batch takes no lsh (LSH levels: ia_synth_levels3)");
     return synth_levels3(levels, n, K, stream);
+}
+
+int ia_batch3_groups(const IaSynthArgs *level_jobs, int K, int *group_of_job) {
+    IA_ARG(level_jobs && group_of_job, "ia_batch3_groups: bad args");
+    IA_ARG(K >= 1 && K <= IA_BATCH_MAX, "ia_batch3_groups: K out of range (1 .. 128)");
+    return batch3_groups(level_jobs, K, group_of_job);
 }
 
 int ia_diag_screen3(const void *db3, long nrows, const double *q165, int M, double *e, double *eps,
@@ -2148,6 +2317,12 @@ int ia_diag_screen3r(const void *db3, const void *dbr, const float *rot, long nr
 int ia_diag_set_color16(int on) {
     const int prev = g_color16.load();
     if (on == 0 || on == 1) g_color16.store(on);
+    return prev;
+}
+
+int ia_diag_set_c3_shared_screen(int on) {
+    const int prev = g_c3_shared_screen.load();
+    if (on == 0 || on == 1) g_c3_shared_screen.store(on);
     return prev;
 }
 

@@ -393,11 +393,16 @@ def rot3_batch_shared():
 def synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=False, check=True, rot_shared=None):
     """K 3-channel analogies of identical shapes in ONE set of launches per wave
     (ia_synth_levels3_batch: k_screen3r and the fused k_exact3<true> with the job as a grid
-    dimension).  Per job and level its own database (ia_db3_build), rotated database
-    (ia_db3_build_rot) and workspace; the rotation is one per batch (the principal directions
-    of job 0's finest level; rot_shared / IA_ROT3_BATCH_SHARED, default 1) or one per job (its
-    own finest level, as IA_ROT3_SHARED within a job): any orthonormal basis keeps the matcher
-    exact, so the results are those of synthesize3_dev per job either way.  The batch form
+    dimension).  Per DB group and level one database (ia_db3_build) and one rotated database
+    (ia_db3_build_rot); per job and level its own workspace and outputs.  A DB group
+    (db_groups) is the jobs whose A and A' pyramids are the same tensors, as the runs of one
+    A / A' pair in multi_main's batches are: they match against the same rows at every level,
+    and a group of more than one job goes through the screen together against one read of its
+    rotated database (k_screen3rs).  Jobs with pyramids of their own are groups of one and run
+    the launches of an unshared batch.  The rotation is one per batch (the principal directions
+    of job 0's finest level; rot_shared / IA_ROT3_BATCH_SHARED, default 1) or one per DB group
+    (its own finest level, as IA_ROT3_SHARED within a job): any orthonormal basis keeps the
+    matcher exact, so the results are those of synthesize3_dev per job either way.  The batch form
     exists for the rotated screen only: with IA_DB_ROT=0 or the exhaustive search
     (IA_COLOR16=0) the jobs run one after the other through synthesize3_dev.  jobs, ks, the
     return value: as synthesize_batch_dev."""
@@ -413,29 +418,55 @@ def synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=False, check=True
     levels = list(range(1, max_levels))
     if not levels:
         return [{} for _ in jobs]
-    built = [{level: _db3_level(A_pyr, Ap_list, level) for level in levels}
-             for A_pyr, Ap_list, _, _ in jobs]
-    rots = []
-    for q in range(K if not rot_shared else 1):
-        Nf, db3f = built[q][levels[-1]][5:7]
-        rots.append(algorithms.rot3_rotation(db3f, Nf))
-    args, keep, res = [], [], [{} for _ in jobs]     # level-major: args[j * K + job]
-    for level in levels:
-        for q, ((_, _, B_pyr, Bp_pyr), kj) in enumerate(zip(jobs, ks)):
-            N, db3 = built[q][level][5:7]
-            rot = rots[q if not rot_shared else 0]
-            dbr = algorithms.rot3_apply(db3, N, rot)
-            a, (s, im, dbg), bufs = _level3_args(built[q][level], rot, dbr, B_pyr, Bp_pyr, level,
-                                                 max_levels, kj, weights, debug)
-            args.append(a)
-            keep.append((bufs, dbr))
-            res[q][level] = (s, im) if dbg is None else (s, im, dbg)
-    arr = (_ia.IaSynthArgs * len(args))(*args)
+    arr, res, keep = _batch3_args(jobs, max_levels, ks, weights, debug, rot_shared)
     _ia.check(lib.ia_synth_levels3_batch(arr, len(levels), K, st), 'ia_synth_levels3_batch')
     if check:
-        _ia.check(lib.ia_synth3_status(arr, len(args), st), 'ia_synth3_status')
-    del keep, built
+        _ia.check(lib.ia_synth3_status(arr, len(arr), st), 'ia_synth3_status')
+    del keep
     return res
+
+
+def db_groups(jobs):
+    """The DB group of each job of a colour batch, numbered in job order: two jobs are in one
+    group when their A pyramids and all their A' pyramids are the same tensors level by level
+    (data_ptr, shape and stride; the same number of A' images).  Identity only: equal contents
+    in distinct tensors are distinct groups (multi_main aliases such pyramids first)."""
+    def ident(A_pyr, Ap_list):
+        return tuple(tuple((p.data_ptr(), tuple(p.shape), p.stride()) for p in pyr)
+                     for pyr in [A_pyr] + list(Ap_list))
+    seen = {}
+    return [seen.setdefault(ident(A_pyr, Ap_list), len(seen)) for A_pyr, Ap_list, _, _ in jobs]
+
+
+def _batch3_args(jobs, max_levels, ks, weights, debug, rot_shared):
+    """The argument array of synthesize3_batch_dev's ia_synth_levels3_batch call (level-major:
+    entry j * K + job), each job's {level: (s, im[, debug])} and the buffers to keep alive until
+    the call has been checked (every shared buffer once).  One database, one rotated database
+    and (without rot_shared) one rotation per DB group (db_groups) and level."""
+    levels = list(range(1, max_levels))
+    group = db_groups(jobs)
+    lead = [group.index(g) for g in range(max(group) + 1)]     # each group's first job
+    built = [{level: _db3_level(jobs[q][0], jobs[q][1], level) for level in levels} for q in lead]
+    rots = []
+    for g in range(len(lead) if not rot_shared else 1):
+        Nf, db3f = built[g][levels[-1]][5:7]
+        rots.append(algorithms.rot3_rotation(db3f, Nf))
+    args, keep, res = [], [built, rots], [{} for _ in jobs]
+    for level in levels:
+        dbrs = {}       # (built at the group's first job: an unshared batch makes its calls in the old order)
+        keep.append(dbrs)
+        for q, ((_, _, B_pyr, Bp_pyr), kj) in enumerate(zip(jobs, ks)):
+            g = group[q]
+            N, db3 = built[g][level][5:7]
+            rot = rots[g if not rot_shared else 0]
+            if g not in dbrs:
+                dbrs[g] = algorithms.rot3_apply(db3, N, rot)
+            a, (s, im, dbg), bufs = _level3_args(built[g][level], rot, dbrs[g], B_pyr, Bp_pyr, level,
+                                                 max_levels, kj, weights, debug)
+            args.append(a)
+            keep.append(bufs)
+            res[q][level] = (s, im) if dbg is None else (s, im, dbg)
+    return (_ia.IaSynthArgs * len(args))(*args), res, keep
 
 
 def synthesize_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights,
@@ -542,8 +573,9 @@ def synthesize_batch_dev(jobs, max_levels, k, weights, prof=False, debug=False, 
     job is synthesised exactly as synthesize_dev would (exact matcher, one GPU); each wave's
     screen and fused kernel serve all K jobs at once (ia_synth_levels_batch), so the batch
     costs about one job's per-wave launch latency.  Jobs of 3-channel pyramids (all of them:
-    a mix raises ValueError) go to synthesize3_batch_dev.  Returns one {level: (s, im[,
-    debug])} dict per job."""
+    a mix raises ValueError) go to synthesize3_batch_dev, where jobs given the same A and A'
+    pyramid tensors share one database per level (luminance jobs always build their own).
+    Returns one {level: (s, im[, debug])} dict per job."""
     K = len(jobs)
     if K == 0:
         return []
@@ -889,12 +921,32 @@ def _run_key(c, A_pyr, Ap_pyr_list, B_pyr):
     return (c.num_ch, c.max_levels, shapes, len(Ap_pyr_list), algorithms.lsh_params(c) is None)
 
 
+def _alias_pyramids(same):
+    """Among the runs of one batch (_multi_batch's `ready` entries), a run whose A and A' file
+    names and setup options equal an earlier run's takes that run's A and A' pyramid objects
+    when every level of every pyramid is bit-equal (torch.equal): the batch then sees them as
+    one DB group (db_groups).  The names only limit the comparisons; the equality makes the
+    aliasing safe (with remap_lum, for one, A depends on B)."""
+    for i, r in enumerate(same):
+        A_pyr, Ap_list = r[3][0], r[3][1]
+        for e in same[:i]:
+            A0, Ap0 = e[3][0], e[3][1]
+            if e[5] != r[5] or A0 is A_pyr or len(Ap0) != len(Ap_list):
+                continue
+            pairs = list(zip(A0, A_pyr)) + [xy for p0, p in zip(Ap0, Ap_list) for xy in zip(p0, p)]
+            if all(x.shape == y.shape and torch.equal(x, y) for x, y in pairs):
+                colour = Ap0 if r[3][4] is Ap_list else r[3][4]   # (convert=False: the A' pyramids)
+                r[3] = (A0, Ap0) + tuple(r[3][2:4]) + (colour,)
+                break
+
+
 def _multi_batch(group, c, debug):
     """multi_main's batched path for the runs `group` ([(j, run)], at most `batch` of them):
     each run is set up under its own copy of the config (its overrides apply to it alone);
     runs that agree on _run_key are synthesised by one synthesize_batch_dev call, each with
     its own kappa, every other run alone; then each run's outputs as image_analogies_main
-    writes them.  Returns {j: B' pyramid}."""
+    writes them.  Batched runs of the same A and A' files share their A and A' pyramids
+    (_alias_pyramids), so a colour batch builds their databases once.  Returns {j: B' pyramid}."""
     import types
     ready = []
     for j, run in group:
@@ -909,13 +961,16 @@ def _multi_batch(group, c, debug):
                                  'c.init_rand', 'c.AB_weight', 'c.k'],
                       [A_fname, Ap_fname_list, B_fname, cj.convert, cj.remap_lum, cj.init_rand,
                        cj.AB_weight, cj.k])
-        ready.append((j, out_path, cj, pyrs, _run_key(cj, pyrs[0], pyrs[1], pyrs[2])))
+        named = (A_fname, tuple(Ap_fname_list), cj.convert, cj.remap_lum, cj.AB_weight,
+                 getattr(cj, 'levels', None), cj.n_sm)
+        ready.append([j, out_path, cj, pyrs, _run_key(cj, pyrs[0], pyrs[1], pyrs[2]), named])
     results = {}
     for key in dict.fromkeys(r[4] for r in ready):          # (first-seen order)
         same = [r for r in ready if r[4] == key]
         c0 = same[0][2]
         weights = _ia.to_dev(c0.weights)
         if len(same) > 1 and key[4]:
+            _alias_pyramids(same)
             res = synthesize_batch_dev([r[3][:4] for r in same], c0.max_levels, [r[2].k for r in same],
                                        weights, debug=debug)
         else:
@@ -924,7 +979,7 @@ def _multi_batch(group, c, debug):
         results.update((r[0], x) for r, x in zip(same, res))
     torch.cuda.synchronize()
     out = {}
-    for j, out_path, cj, pyrs, _ in ready:
+    for j, out_path, cj, pyrs, _, _ in ready:
         write_outputs(results[j], pyrs[3], pyrs[4], cj, out_path, debug)
         out[j] = [p.cpu().numpy() for p in pyrs[3]]
     return out
@@ -941,7 +996,12 @@ def multi_main(runs, c, debug=False, rank=None, world=None, batch=0):
     order in groups of at most K, and the runs of a group that agree on the channel count,
     max_levels, every pyramid shape, the number of A' images and the exact matcher are
     synthesised by ONE synthesize_batch_dev call (luminance or 3-channel), each with its own
-    kappa; every other run goes alone.  A batched run writes the same files with the same
+    kappa; every other run goes alone.  Runs of one such call that name the same A and A'
+    files under the same convert, remap_lum, AB_weight, levels and n_sm, and whose A and A'
+    pyramids then are bit-equal (multi_script.py's 8 runs per material), share those pyramids:
+    a 3-channel batch builds one database and one rotated database per level for them and
+    screens their queries together (synthesize3_batch_dev); runs with other A / A' files join
+    the batch as DB groups of their own.  A batched run writes the same files with the same
     bytes as an unbatched one; on this path a run's overrides apply to that run only (each run
     takes a copy of `c`), while the unbatched loop sets them on `c` itself as before.
     Returns {j: B' pyramid} of this rank's runs."""

@@ -384,8 +384,19 @@ int ia_synth_levels3(const IaSynthArgs *levels, int n, void *stream);
  * 1 <= K <= 128; K = 1 is ia_synth_levels3.  IA_E_ARG (nothing launched) when the jobs differ
  * in a shape (H, W, B_hs, B_ws, src.Ah / Aw / A_hs / A_ws / nAp, nrows), in having debug
  * outputs or dbr / rot, when a job has a comm (for any K: batches shard by job), an lsh or a
- * partial row range, and when K > 1 without the rotated DB (the batch form exists for the R16c screen only). */
+ * partial row range, and when K > 1 without the rotated DB (the batch form exists for the R16c screen only).
+ * Jobs of a level may pass the same dbr (the multi_script batch: runs of one A / A' pair have
+ * the same database at every level): they form a DB group and must then pass the same db, rot,
+ * nrows and src image pointers too (IA_E_ARG naming the field otherwise).  Nothing is written
+ * into those buffers during synthesis.  With fewer groups than jobs the wave's screen is
+ * k_screen3rs, which reads a group's rotated DB once for the query tiles of all its jobs;
+ * a batch without shared databases runs the launches it always ran.  Same results either way. */
 int ia_synth_levels3_batch(const IaSynthArgs *levels, int n, int K, void *stream);
+/* the DB groups of one level's K jobs (level_jobs[0 .. K), 1 <= K <= 128), as
+ * ia_synth_levels3_batch derives them: group_of_job[k] = the group of job k, groups numbered in
+ * order of first appearance, two jobs in one group when they pass the same non-null dbr.
+ * Returns the number of groups, or IA_E_ARG.  Pointer comparison on the host: no device call. */
+int ia_batch3_groups(const IaSynthArgs *level_jobs, int K, int *group_of_job);
 /* the rotated split screen for 3-channel rows (R16c): after ia_db3_build, the
  * caller takes the principal directions V of the level's centred rows (165 x 165, columns by
  * decreasing variance; any V orthonormal to fp64 precision keeps the matcher exact: checked,

@@ -138,6 +138,10 @@ int ia_diag_screen_trace(void *buf);
  * 32)), eps3 and |q'|^2 per query */
 int ia_diag_set_color16(int on);
 int ia_diag_color16_stats(unsigned long long *out);
+/* a colour batch whose jobs share databases (ia_synth_levels3_batch, ia_batch3_groups) for this
+ * process (IA_C3_SHARED_SCREEN): 1 [default] one k_screen3rs pass per DB group, 0 every job
+ * through k_screen3rb; same minima; returns the previous value, -1 leaves it */
+int ia_diag_set_c3_shared_screen(int on);
 int ia_diag_screen3(const void *db3, long nrows, const double *q165, int M, double *e, double *eps,
                     double *qn);
 /* with IA_XW_TRACE=<level tag>: the fused kernel's phase stamps of that level (100 MHz

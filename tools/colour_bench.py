@@ -7,7 +7,12 @@ usage: python tools/colour_bench.py [H W] [steps] [jobs]   (default 180 117 (c1 
        jobs = K > 1: a batch of K colour jobs of that size with distinct seeds in one
        synthesize_batch_dev call (ia_synth_levels3_batch): ms per step and per job, every
        step's time, the candidate tiles per query, under one rotation per batch and one per
-       job (IA_ROT3_BATCH_SHARED both ways)
+       job (IA_ROT3_BATCH_SHARED both ways), and the peak device memory allocated
+       python tools/colour_bench.py H W steps K --shared [G]
+       the same batch with G distinct (A, A') pairs (default 1; job q takes pair q mod G) and K
+       distinct B images and B' seeds: the jobs of a pair are given the same pyramid tensors, so
+       they form one DB group (one database and one rotated database per level, screened
+       together by k_screen3rs; IA_C3_SHARED_SCREEN=0: by k_screen3rb as an unshared batch)
        python tools/colour_bench.py H W steps --shards G [G ...]
        the per-rank cost of the sharded colour synthesis in the manner of tools/shard_sim.py: rank
        0 of G row shards (every level sharded: IA_SHARD_MIN_ROWS defaults to 0 here) over a 1-rank
@@ -44,8 +49,9 @@ import torch  # noqa: E402
 ip, cfg, ia = bench.ip, bench.cfg, bench.ia
 
 
-def batch_main(H, W, steps, K):
-    """K colour jobs of H x W with distinct seeds as one batch."""
+def batch_main(H, W, steps, K, pairs=None):
+    """K colour jobs of H x W with distinct seeds as one batch; pairs = G: G distinct (A, A')
+    among them, each pair's pyramids built once per step and given to all its jobs."""
     import ctypes
     import _ia
     from scipy.ndimage import gaussian_filter
@@ -65,16 +71,19 @@ def batch_main(H, W, steps, K):
         B = np.dstack([bench.smooth_noise(8 + 17 * c + 101 * q, (H, W)) for c in range(3)])
         init = [torch.as_tensor(x).to(dev) for x in ip.initialize_Bp([np.empty(s) for s in shapes], True, 9 + q)]
         srcs.append(tuple(torch.as_tensor(x).to(dev) for x in (A, Ap, B)) + (init, [x.clone() for x in init]))
-    out = {'size': [H, W], 'jobs': K, 'steps': steps, 'pixels_per_job': pixels}
+    out = {'size': [H, W], 'jobs': K, 'steps': steps, 'pixels_per_job': pixels, 'a_pairs': pairs or K}
     st = (ctypes.c_ulonglong * 2)()
     for name, shared in (('rotation_per_batch', True), ('rotation_per_job', False)):
         def step():
             jobs = []
-            for a, ap, b, init, Bp in srcs:
+            for q, (a, ap, b, init, Bp) in enumerate(srcs):
                 for d, s in zip(Bp, init):
                     d.copy_(s)
-                jobs.append((ip.gaussian_pyramid_dev(a, cfg.n_sm), [ip.gaussian_pyramid_dev(ap, cfg.n_sm)],
-                             ip.gaussian_pyramid_dev(b, cfg.n_sm), Bp))
+                if pairs and q >= pairs:
+                    A_pyr, Ap_list = jobs[q % pairs][:2]
+                else:
+                    A_pyr, Ap_list = ip.gaussian_pyramid_dev(a, cfg.n_sm), [ip.gaussian_pyramid_dev(ap, cfg.n_sm)]
+                jobs.append((A_pyr, Ap_list, ip.gaussian_pyramid_dev(b, cfg.n_sm), Bp))
             ia.synthesize3_batch_dev(jobs, L, [0.5] * K, w, rot_shared=shared)
 
         _ia.check(_ia.lib().ia_diag_color16_stats(st), 'stats')   # (reads and clears)
@@ -84,6 +93,7 @@ def batch_main(H, W, steps, K):
         cand = (st[0] / (pixels * K), int(st[1]))
         step()                                                   # (second warm-up)
         torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
         times = []
         for _ in range(steps):
             t0 = time.perf_counter()
@@ -93,7 +103,7 @@ def batch_main(H, W, steps, K):
         med = float(np.median(times))
         out[name] = {'ms_per_step': med, 'ms_per_job': med / K, 'ms_steps': [round(t, 3) for t in times],
                      'px_per_s': pixels * K / (med * 1e-3), 'candidate_tiles_per_query': cand[0],
-                     'full_scans': cand[1],
+                     'full_scans': cand[1], 'peak_mb': round(torch.cuda.max_memory_allocated() / 2 ** 20, 1),
                      'bp_checksum': float(sum(float(x.sum()) for s in srcs for x in s[4][1:L]))}
     print(json.dumps(out))
 
@@ -233,7 +243,11 @@ def main():
     if '--shards' in sys.argv:
         return shards_main(H, W, steps, [int(g) for g in sys.argv[sys.argv.index('--shards') + 1:]] or [1, 2, 4, 8])
     if len(sys.argv) > 4 and int(sys.argv[4]) > 1:
-        return batch_main(H, W, steps, int(sys.argv[4]))
+        pairs = None
+        if '--shared' in sys.argv:
+            rest = sys.argv[sys.argv.index('--shared') + 1:]
+            pairs = max(1, min(int(rest[0]), int(sys.argv[4]))) if rest else 1
+        return batch_main(H, W, steps, int(sys.argv[4]), pairs)
     from scipy.ndimage import gaussian_filter
     dev = 'cuda:0'
     A = np.dstack([bench.smooth_noise(7 + 17 * c, (H, W)) for c in range(3)])
