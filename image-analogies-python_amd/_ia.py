@@ -128,6 +128,8 @@ _SIGS = {
                                               _dp]),
     'ia_batch3_groups': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_int)]),
+    'ia_batch_groups': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.c_int,
+                                       ctypes.POINTER(ctypes.c_int)]),
     'ia_db3_rot_bytes': (ctypes.c_size_t, [ctypes.c_long]),
     'ia_db3_rot_components': (ctypes.c_int, []),
     'ia_db3_rot_floats': (ctypes.c_int, []),
@@ -191,6 +193,10 @@ _SIGS = {
     'ia_diag_set_color16': (ctypes.c_int, [ctypes.c_int]),
     'ia_diag_color16_stats': (ctypes.c_int, [_dp]),
     'ia_diag_set_c3_shared_screen': (ctypes.c_int, [ctypes.c_int]),
+    'ia_diag_set_shared_screen': (ctypes.c_int, [ctypes.c_int]),
+    'ia_diag_shared_screen_waves': (ctypes.c_long, []),
+    'ia_diag_shared_screen_groups': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int,
+                                                    ctypes.POINTER(ctypes.c_int)]),
     'ia_diag_screen3': (ctypes.c_int, [_dp, ctypes.c_long, _dp, ctypes.c_int, _dp, _dp, _dp]),
     'ia_diag_xwave_trace': (ctypes.c_int, [_dp]),
     'ia_diag_set_db_build_form': (ctypes.c_int, [ctypes.c_int]),

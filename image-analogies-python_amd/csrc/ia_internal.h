@@ -275,6 +275,9 @@ struct XJob {
     gptr<const unsigned char> askc;                 // R16 per-segment skip codes (nullable)
 };
 constexpr int IA_BATCH_MAX = 128;
+// a batch's DB group table, staged behind its K job entries (k_screen16rs): the number of DB
+// groups, the jobs of each group, the jobs in group order
+constexpr int IA_GTAB_INTS = 1 + 2 * IA_BATCH_MAX;
 
 // one launch of the fused per-wave kernel k_xwave (ia_xwave.hip): wave t's exact stage,
 // exchange (f.px) and per-pixel tail, and wave t + 1's query rows
@@ -391,6 +394,10 @@ int launch_query_wave(const ImgPair &B, const ImgPair &Bp, int t, int y_lo, int 
 int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Float16 *q16, int M,
                      float *segmin, hipStream_t st, const XJob *jobs = nullptr, int njobs = 1, int parity = 0,
                      bool compact = false);
+// the rotated screen of a batch whose jobs share rotated DBs (k_screen16rs): one launch for the
+// DB groups of gcount[0 .. ngroups) jobs each; jobs / gtab: the device job and group tables
+int launch_screen16rs(const XJob *jobs, const int *gtab, const int *gcount, int ngroups, long nrows,
+                      const StageMap &sm, int M, hipStream_t st, int parity);
 // amax = max(amax, the split scale's bound of a level's four value ranges) (ia_features.hip);
 // part: DBB_BLOCKS x 8 doubles of scratch
 int launch_db_amax(const IaSrcLevel *src, const DbSrc &d, const double *center, float *amax,

@@ -19,6 +19,7 @@
 // LDS 8 segments at a time.
 #include "ia_internal.h"
 #include "ia_rot16.h"
+#include "../../include/ia_diag.h"
 
 #include <float.h>
 #include <type_traits>
@@ -509,6 +510,166 @@ __global__ __launch_bounds__(256, IA_R16_OCC) void k_screen16r(const half8 *__re
     else if (wv == 1) r16_body<G, 1>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
     else if (wv == 2) r16_body<G, 2>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
     else r16_body<G, 3>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+}
+
+// ---- the shared form (k_screen16rs): a batch whose jobs share rotated databases ----------
+// A DB group (ia_batch_groups) is the jobs of a level passing one dbr.  Its n jobs' query tiles
+// (T = ceil(M / 32) each, jobs in group order) form one list of nT tiles, cut into
+// ceil(nT / MAX_G) query groups of as equal size as possible (sq_split); a query group may start
+// and end inside a job.  A workgroup owns a (part, query group) pair as in k_screen16r and
+// streams the group's rows ONCE for all its tiles, whichever jobs they belong to: tile i's 32
+// query rows come from its job's q16[parity], its minima go to its job's segmin.  The launch is
+// built for the widest query group (G); a narrower one repeats its first tile in the spare
+// slots and writes nothing for them.
+// The host stages the group table behind the job table (IA_GTAB_INTS ints: the number of DB
+// groups, the jobs per group, the jobs in group order); the per-tile (job, tile) pairs follow
+// from it and M, so one table serves every wave of the level.
+__host__ __device__ inline void sq_split(int nT, int qg, int &first, int &count) {
+    const int ng = (nT + MAX_G - 1) / MAX_G, base = nT / ng, rem = nT - base * ng;
+    first = qg * base + (qg < rem ? qg : rem);
+    count = base + (qg < rem ? 1 : 0);
+}
+
+// r16_body's row loop as a copy (as k_screen3rs has one: k_screen16r, k_screen16c and
+// k_screen16w keep their instructions whatever changes here): the query operands and the
+// minima's destinations are per tile (qt, sp, lim in LDS: tile i's 32 query rows, its segmin
+// rows and how many of them are real queries)
+template <int G, int W>
+__device__ __forceinline__ void r16_body_s(const half8 *__restrict__ db16, half8 *sbuf, int *smin,
+                                           const StageMap &sm, long chunk, int s0, int nstage, int tps,
+                                           const half8 *const *qt, float *const *sp, const int *lim,
+                                           long seg0, long nseg) {
+    constexpr int NS = R16_S16 ? c16_ns<G, W>() : bal_ns(G, W);
+    constexpr int T0 = bal_t0(G, W);
+    constexpr int TH8 = R16_TILE_H8, SH8 = STAGE_TILES * TH8, NP = SH8 / 256;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    half8 bq[NS][R16_S16 ? 2 : R16_MFMA];
+    if constexpr (R16_S16) {
+        // query block B = T + k is rows 16 (B % 2) .. + 15 of tile B / 2 (operands as r16_body)
+        const int q = lane >> 4, c = lane & 15;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            constexpr int B0 = c16_t0<G, W>();
+            const half8 *p = qt[(B0 + k) >> 1] + (long)(((B0 + k) & 1) * 16 + c) * Q16_ROW + (q & 1) * R16_MFMA + (q >> 1);
+            bq[k][0] = p[0];
+            bq[k][1] = p[2];
+        }
+    } else {
+        const int j = lane & 31, h = lane >> 5;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const half8 *p = qt[T0 + k] + (long)j * Q16_ROW + h * R16_MFMA;
+#pragma unroll
+            for (int m = 0; m < R16_MFMA; ++m) bq[k][m] = p[m];
+        }
+    }
+    auto issue = [&](int s) {
+        const half8 *src = db16 + (stage_lrow(sm, chunk, s0 + s) >> 5) * TH8 + W * 64 + lane;
+        half8 *dst = sbuf + (s % R16_RING) * SH8 + W * 64;
+#pragma unroll
+        for (int k = 0; k < NP; ++k)
+            __builtin_amdgcn_global_load_lds((const void *)(src + k * 256), (void *)(dst + k * 256), 16, 0, 2);
+    };
+    float mn[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) mn[k] = FLT_MAX;
+    const int spc = nstage * STAGE_TILES / tps;
+#pragma unroll
+    for (int s = 0; s < R16_RING - 1; ++s)
+        if (s < nstage) issue(s);
+    if (nstage > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (R16_RING - 2)) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stage_barrier();
+    for (int s = 0; s < nstage; ++s) {
+        const bool more = s + R16_RING - 1 < nstage;
+        if (more) issue(s + R16_RING - 1);
+        if constexpr (R16_S16) {
+            r16_stage_s16<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
+            r16_close_s16<G, W, NS>(s, tps, smin, mn, lane);
+        } else {
+            r16_stage<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
+            r16_close<G, W, NS>(s, tps, smin, mn, lane);
+        }
+        const int done = (s + 1) * STAGE_TILES;
+        if (done % tps == 0) {
+            const int sg = done / tps - 1;
+            if (sg % SPC_STAGE == SPC_STAGE - 1 || sg == spc - 1) {
+                stage_barrier();
+                const int base = sg - sg % SPC_STAGE, n = sg - base + 1;
+                for (int i = tid; i < G * 32 * n; i += 256) {
+                    const int ql = i / n, k = i - ql * n;
+                    int *e = &smin[k * (G * 32) + ql];
+                    const int tl = ql >> 5, l = ql & 31;
+                    if (l < lim[tl]) {
+                        float *dst = sp[tl] + ((long)l * nseg + seg0 + base + k);
+                        if constexpr (IA_R16_NTMIN) __builtin_nontemporal_store(fkey_inv(*e), dst);
+                        else *dst = fkey_inv(*e);
+                    }
+                    *e = 0x7fffffff;
+                }
+            }
+        }
+        if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (R16_RING - 2)) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        stage_barrier();
+    }
+}
+
+// grid: (nchunks x split rounded up to 8) x nqg, XCD-aware as k_screen16r (all query groups of
+// a part share blockIdx % 8); nqg: the query groups of every DB group, in group order
+template <int G>
+__global__ __launch_bounds__(256, IA_R16_OCC) void k_screen16rs(const XJob *__restrict__ jobs,
+                                                       const int *__restrict__ gtab, int nchunks, int ch,
+                                                       int seg_rows, StageMap sm, int M, int nqg, long nseg,
+                                                       int parity, int split) {
+    __shared__ half8 sbuf[R16_RING * STAGE_H8];
+    __shared__ int smin[SPC_STAGE * G * 32];
+    __shared__ const half8 *qt[G];
+    __shared__ float *sp[G];
+    __shared__ int lim[G];
+    const int b = blockIdx.x;
+    const int slot = b >> 3;
+    const int part = (slot / nqg) * 8 + (b & 7);
+    if (part >= nchunks * split) return;   // uniform over the block, before any barrier
+    // the block's DB group (n jobs from position pos of the group order) and query group qg in it
+    const int T = (M + 31) >> 5, ngroups = gtab[0];
+    int qg = slot - (slot / nqg) * nqg, g = 0, pos = 0, n = gtab[1];
+    while (g + 1 < ngroups) {
+        const int here = (n * T + MAX_G - 1) / MAX_G;
+        if (qg < here) break;
+        qg -= here;
+        pos += n;
+        n = gtab[1 + ++g];
+    }
+    int first, count;
+    sq_split(n * T, qg, first, count);
+    count = count < G ? count : G;
+    if (first + count > n * T) first = count = 0;   // (a grid of another table: writes nothing)
+    const int *order = gtab + 1 + IA_BATCH_MAX + pos;
+    if (threadIdx.x < G) {
+        const int i = threadIdx.x, ti = first + (i < count ? i : 0);
+        const int jp = ti / T, tj = ti - jp * T;
+        const XJob &J = jobs[order[jp]];
+        qt[i] = reinterpret_cast<const half8 *>(J.q16[parity].get()) + (long)tj * 32 * Q16_ROW;
+        sp[i] = J.segmin.get() + (long)tj * 32 * nseg;
+        lim[i] = i < count ? (M - 32 * tj < 32 ? M - 32 * tj : 32) : 0;
+    }
+    const half8 *db16 = reinterpret_cast<const half8 *>(jobs[order[0]].dbr.get());
+    const int lsp = __builtin_ctz((unsigned)split);
+    const int chunk = part >> lsp, half = part & (split - 1);
+    const int spc = ch / seg_rows;
+    for (int i = threadIdx.x; i < SPC_STAGE * G * 32; i += 256) smin[i] = 0x7fffffff;
+    const int nstage = (ch / (STAGE_TILES * 32)) >> lsp;
+    const int tps = seg_rows >> 5;
+    const long seg0 = (long)chunk * spc + (long)half * (spc >> lsp);
+    const int s0 = half * nstage;
+    __syncthreads();   // the tile table (before any stage is in flight)
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wv == 0) r16_body_s<G, 0>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qt, sp, lim, seg0, nseg);
+    else if (wv == 1) r16_body_s<G, 1>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qt, sp, lim, seg0, nseg);
+    else if (wv == 2) r16_body_s<G, 2>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qt, sp, lim, seg0, nseg);
+    else r16_body_s<G, 3>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qt, sp, lim, seg0, nseg);
 }
 
 // the compact screen (ia_rot16.h RK_*; one job): k_screen16r's grid, parts and minima over the
@@ -1017,6 +1178,69 @@ int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Flo
     return IA_OK;
 }
 
+// the shared form's query groups for DB groups of gcount[0 .. ngroups) jobs and M queries per job:
+// their number, and the widest one's tiles (the kernel instance)
+static int shared_qgroups(const int *gcount, int ngroups, int M, int *widest) {
+    const int T = (M + 31) / 32;
+    int nqg = 0, G = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        const int nT = gcount[g] * T, ng = (nT + MAX_G - 1) / MAX_G;
+        nqg += ng;
+        G = std::max(G, (nT + ng - 1) / ng);
+    }
+    if (widest) *widest = G;
+    return nqg;
+}
+
+int launch_screen16rs(const XJob *jobs, const int *gtab, const int *gcount, int ngroups, long nrows,
+                      const StageMap &sm, int M, hipStream_t st, int parity) {
+    const int ch = db_chunk_rows(nrows);
+    const long nchunks = db_nchunks(nrows);
+    const int seg_rows = db_seg_rows(nrows);
+    const long nseg = db_nsegs(nrows);
+    IA_ARG(M > 0 && ch % (STAGE_TILES * 32) == 0 && seg_rows % (STAGE_TILES * 32) == 0 &&
+               ch / seg_rows <= SPC_MAX,
+           "launch_screen16rs: bad chunking");
+    IA_ARG(sm.sc == ch / 128, "launch_screen16rs: stage map of another chunking");
+    IA_ARG(jobs && gtab && gcount && ngroups >= 1 && ngroups <= IA_BATCH_MAX, "launch_screen16rs: bad batch");
+    int G = 0;
+    const int nqg = shared_qgroups(gcount, ngroups, M, &G);
+    static const long cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+        return (long)n;
+    }();
+    // parts per chunk as launch_screen16r, by the launch's total block count
+    const int spc = ch / seg_rows;
+    int split = 1;
+    while (2 * split <= spc && nchunks * 2 * split * nqg <= cus * IA_R16_OCC) split *= 2;
+    const long nb = ((nchunks * split + 7) / 8) * 8 * nqg;
+    IA_ARG(nb < (1L << 31), "screen grid too large");
+#define IA_R16S_CASE(GG)                                                                            \
+    case GG:                                                                                        \
+        k_screen16rs<GG><<<(unsigned)nb, 256, 0, st>>>(jobs, gtab, (int)nchunks, ch, seg_rows, sm, M, \
+                                                       nqg, nseg, parity, split);                   \
+        break;
+    switch (G) {
+        IA_R16S_CASE(1)
+        IA_R16S_CASE(2)
+        IA_R16S_CASE(3)
+        IA_R16S_CASE(4)
+        IA_R16S_CASE(5)
+        IA_R16S_CASE(6)
+        IA_R16S_CASE(7)
+        IA_R16S_CASE(8)
+        IA_R16S_CASE(9)
+        IA_R16S_CASE(10)
+        IA_R16S_CASE(11)
+        default: set_error("launch_screen16rs: bad query split"); return IA_E_ARG;
+    }
+#undef IA_R16S_CASE
+    IA_LAUNCH_CHECK("k_screen16rs");
+    return IA_OK;
+}
+
 int launch_query_rows_r16(const double *q64, int M, const double *center, const float *rot,
                           const float *amax, double *nq, double *nsk, _Float16 *q16, hipStream_t st,
                           bool compact = false) {
@@ -1065,6 +1289,33 @@ int ia_diag_set_r16_form(int form) {
     const int prev = r16_form();
     if (form == 0 || form == 1) g_r16_form.store(form);
     return prev;
+}
+
+int ia_diag_shared_screen_groups(const int *jobs_per_group, int G, int M, int *out) {
+    IA_ARG(jobs_per_group && G >= 1 && G <= IA_BATCH_MAX && M > 0, "ia_diag_shared_screen_groups: bad args");
+    int K = 0;
+    for (int g = 0; g < G; ++g) {
+        IA_ARG(jobs_per_group[g] >= 1, "ia_diag_shared_screen_groups: an empty DB group");
+        K += jobs_per_group[g];
+    }
+    IA_ARG(K <= IA_BATCH_MAX, "ia_diag_shared_screen_groups: more than 128 jobs");
+    const int T = (M + 31) / 32;
+    int nqg = 0;
+    for (int g = 0; g < G; ++g) {
+        const int nT = jobs_per_group[g] * T, ng = (nT + MAX_G - 1) / MAX_G;
+        for (int qg = 0; qg < ng; ++qg, ++nqg) {
+            if (!out) continue;
+            int *o = out + (size_t)nqg * IA_SHARED_QG_INTS;
+            int first, count;
+            sq_split(nT, qg, first, count);
+            o[0] = g; o[1] = first; o[2] = count;
+            for (int i = 0; i < MAX_G; ++i) {
+                o[3 + 2 * i] = i < count ? (first + i) / T : -1;
+                o[4 + 2 * i] = i < count ? (first + i) % T : -1;
+            }
+        }
+    }
+    return nqg;
 }
 
 int ia_db_rot_components(void) { return R16_P; }

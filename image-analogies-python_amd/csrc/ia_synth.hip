@@ -186,7 +186,7 @@ struct SynthWs {
     double *nqb;
     unsigned long long *dbox;
     unsigned int *ctl;
-    XJob *jtab;              // a batch's job table (ia_synth_levels_batch, job 0's workspace)
+    XJob *jtab;              // a batch's job table, then its DB group table (ia_synth_levels_batch, job 0's workspace)
     unsigned long long *xbox;   // split candidates: the helpers' records, 8 granules per row
 };
 constexpr int XW_CTL_ERR = 2;
@@ -213,7 +213,7 @@ static size_t carve(SynthWs *ws, char *base, int H, int W, long nrows, int nrank
     w.nqb = (double *)take((size_t)qr * sizeof(double));
     w.dbox = (unsigned long long *)take((size_t)H * 2 * sizeof(unsigned long long));
     w.ctl = (unsigned int *)take(256);
-    w.jtab = (XJob *)take((size_t)IA_BATCH_MAX * sizeof(XJob));
+    w.jtab = (XJob *)take((size_t)IA_BATCH_MAX * sizeof(XJob) + IA_GTAB_INTS * sizeof(int));
     w.xbox = (unsigned long long *)take((size_t)H * 8 * sizeof(unsigned long long));
     if (ws) *ws = w;
     return off;
@@ -334,6 +334,27 @@ static long xsplit_min_rows() { return g_xsplit_min_rows.load(std::memory_order_
 // (eligible: one unsharded job's strip-form R16 level), else one
 static int xsplit_grid(bool eligible, long nrows, int R) {
     return eligible && nrows >= xsplit_min_rows() && db_nsegs(nrows) <= (1L << 20) ? 2 * R : R;
+}
+
+// IA_SHARED_SCREEN (ia_diag_set_shared_screen): 1 a batch whose jobs share rotated databases
+// screens them in one k_screen16rs launch per wave, 0 every job through the K-job k_screen16r
+static std::atomic<int> g_shared_screen{env_int("IA_SHARED_SCREEN", 1) != 0};
+// waves whose screen was k_screen16rs (ia_diag_shared_screen_waves)
+static std::atomic<long> g_shared_waves{0};
+
+// a job's database: its rotated rows where it has them, else the image form, else the rows
+static const void *job_db(const IaSynthArgs &a) { return a.dbr ? a.dbr : a.dbi ? a.dbi : a.db; }
+// the DB groups of one level's K jobs (ia_batch_groups): jobs passing the same non-null database
+// form a group, numbered in order of first appearance; returns their number
+static int batch_groups(const IaSynthArgs *jobs, int K, int *group_of_job) {
+    int G = 0, first[IA_BATCH_MAX];
+    for (int k = 0; k < K; ++k) {
+        int g = 0;
+        while (g < G && !(job_db(jobs[k]) && job_db(jobs[first[g]]) == job_db(jobs[k]))) ++g;
+        if (g == G) first[G++] = k;
+        group_of_job[k] = g;
+    }
+    return G;
 }
 
 int screen16_attributes(bool img, hipFuncAttributes *at);
@@ -626,9 +647,30 @@ struct LevelRun {
         }
         pinned[0] = job_entry();
         for (int k = 1; k < K; ++k) pinned[k] = part[k - 1].job_entry();
-        IA_HIP(hipMemcpyAsync(ws.jtab, pinned, (size_t)K * sizeof(XJob), hipMemcpyHostToDevice, st));
+        // the DB groups (the caller has checked that jobs of one database agree in everything read
+        // with it): jobs per group and the jobs in group order, behind the job entries
+        int grp[IA_BATCH_MAX];
+        const int G = batch_groups(args, K, grp);
+        int *gt = reinterpret_cast<int *>(pinned + K);
+        gt[0] = G;
+        gcount.assign(G, 0);
+        for (int k = 0; k < K; ++k) ++gcount[grp[k]];
+        for (int g = 0, i = 0; g < IA_BATCH_MAX; ++g) {
+            gt[1 + g] = g < G ? gcount[g] : 0;
+            for (int k = 0; k < K && g < G; ++k)
+                if (grp[k] == g) gt[1 + IA_BATCH_MAX + i++] = k;
+        }
+        for (int i = K; i < IA_BATCH_MAX; ++i) gt[1 + IA_BATCH_MAX + i] = 0;
+        shared_screen = G < K && plan.r16 && g_shared_screen.load(std::memory_order_relaxed) != 0;
+        IA_HIP(hipMemcpyAsync(ws.jtab, pinned, batch_table_bytes(K), hipMemcpyHostToDevice, st));
         return IA_OK;
     }
+    // a batch's staged tables: K job entries, then the DB group table
+    static size_t batch_table_bytes(int K) { return (size_t)K * sizeof(XJob) + IA_GTAB_INTS * sizeof(int); }
+    // a batch's DB groups: jobs per group; shared_screen: some jobs share a rotated database and
+    // the wave's screen is k_screen16rs (else the K-job k_screen16r, every job for itself)
+    std::vector<int> gcount;
+    bool shared_screen = false;
 
     // wave t on the fused path: [wave 0's query rows,] the screen, then k_xwave (exact
     // stage, exchange, tail, and wave t + 1's query rows into the other buffer set)
@@ -654,7 +696,12 @@ struct LevelRun {
         hipEvent_t e0 = wave_event(0), e1 = wave_event(1);
         if (e0) IA_HIP(hipEventRecord(e0, sq));
         const bool cmp = plan.rk && (wave_compact(W, t) || (plan.rkcol && wave_compact_col(W, t)));
-        if (r16) {
+        if (r16 && shared_screen) {
+            if ((rc = launch_screen16rs(ws.jtab, reinterpret_cast<const int *>(ws.jtab + K), gcount.data(),
+                                        (int)gcount.size(), v.nrows, v.sm, M, sq, b)))
+                return rc;
+            g_shared_waves.fetch_add(1, std::memory_order_relaxed);
+        } else if (r16) {
             if ((rc = launch_screen16r(cmp ? a->dbk : a->dbr, v.nrows, v.sm, q16s[b], M, segmin, sq, xa.jobs, K, b,
                                        cmp)))
                 return rc;
@@ -1047,7 +1094,7 @@ static int synth_levels(const IaSynthArgs *levels, int n, int K, void *stream) {
     // the previous call's copies have run)
     XJob *pinned = nullptr;
     if (K > 1) {
-        IA_HIP(g_pipe.staging((size_t)n * K * sizeof(XJob), reinterpret_cast<void **>(&pinned)));
+        IA_HIP(g_pipe.staging((size_t)n * LevelRun::batch_table_bytes(K), reinterpret_cast<void **>(&pinned)));
     }
     // Levels whose DB is sharded over several ranks and exchanged over RCCL never overlap
     // one another: each one's first wave waits for the previous such level's last.  RCCL's
@@ -1073,7 +1120,10 @@ static int synth_levels(const IaSynthArgs *levels, int n, int K, void *stream) {
     std::vector<PipeLevel> pl(n);
     for (int j = 0; j < n; ++j) {
         if ((rc = g_pipe.level_begin(j)) ||
-            (rc = run[j].init_batch(&levels[(size_t)j * K], K, g_pipe.stream(j), pinned + (size_t)j * K)))
+            (rc = run[j].init_batch(&levels[(size_t)j * K], K, g_pipe.stream(j),
+                                    K > 1 ? reinterpret_cast<XJob *>(reinterpret_cast<char *>(pinned) +
+                                                                     (size_t)j * LevelRun::batch_table_bytes(K))
+                                          : nullptr)))
             return rc;
         // (on the fused path wave t's launch also builds wave t + 1's query rows)
         pl[j] = PipeLevel{run[j].H, run[j].W, run[j].plan.xw, multi_rank(j)};
@@ -1091,7 +1141,36 @@ static int synth_levels(const IaSynthArgs *levels, int n, int K, void *stream) {
 int ia_synth_levels(const IaSynthArgs *levels, int n, void *stream) { return synth_levels(levels, n, 1, stream); }
 
 int ia_synth_levels_batch(const IaSynthArgs *levels, int n, int K, void *stream) {
+    // jobs of a level that pass one database are one DB group (ia_batch_groups): it stands for
+    // one level index, so everything read with it is the same memory too
+    for (int j = 0; levels && j < n && n <= 64 && K > 1 && K <= IA_BATCH_MAX; ++j)
+        for (int k = 1; k < K; ++k) {
+            const IaSynthArgs &b = levels[(size_t)j * K + k];
+            for (int p = 0; p < k; ++p) {
+                const IaSynthArgs &c = levels[(size_t)j * K + p];
+                if (!((b.db && b.db == c.db) || (b.dbi && b.dbi == c.dbi) || (b.dbr && b.dbr == c.dbr))) continue;
+#define IA_SAME(field) IA_ARG(b.field == c.field, "ia_synth_levels_batch: jobs sharing a database differ in " #field)
+                IA_SAME(db); IA_SAME(dbi); IA_SAME(dbr); IA_SAME(dbk); IA_SAME(rot); IA_SAME(center); IA_SAME(amax);
+                IA_SAME(row0); IA_SAME(nrows);
+                IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg);
+#undef IA_SAME
+            }
+        }
     return synth_levels(levels, n, K, stream);
 }
+
+int ia_batch_groups(const IaSynthArgs *level_jobs, int K, int *group_of_job) {
+    IA_ARG(level_jobs && group_of_job, "ia_batch_groups: bad args");
+    IA_ARG(K >= 1 && K <= IA_BATCH_MAX, "ia_batch_groups: K out of range (1 .. 128)");
+    return batch_groups(level_jobs, K, group_of_job);
+}
+
+int ia_diag_set_shared_screen(int on) {
+    const int prev = g_shared_screen.load();
+    if (on == 0 || on == 1) g_shared_screen.store(on);
+    return prev;
+}
+
+long ia_diag_shared_screen_waves(void) { return g_shared_waves.load(std::memory_order_relaxed); }
 
 }  // extern "C"

@@ -427,9 +427,9 @@ def synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=False, check=True
 
 
 def db_groups(jobs):
-    """The DB group of each job of a colour batch, numbered in job order: two jobs are in one
-    group when their A pyramids and all their A' pyramids are the same tensors level by level
-    (data_ptr, shape and stride; the same number of A' images).  Identity only: equal contents
+    """The DB group of each job of a batch (colour or luminance), numbered in job order: two
+    jobs are in one group when their A pyramids and all their A' pyramids are the same tensors
+    level by level (data_ptr, shape and stride; the same number of A' images).  Identity only: equal contents
     in distinct tensors are distinct groups (multi_main aliases such pyramids first)."""
     def ident(A_pyr, Ap_list):
         return tuple(tuple((p.data_ptr(), tuple(p.shape), p.stride()) for p in pyr)
@@ -572,9 +572,15 @@ def synthesize_batch_dev(jobs, max_levels, k, weights, prof=False, debug=False, 
     pyramids (Bp_pyr updated in place); k: one kappa or one per job.  Every level of every
     job is synthesised exactly as synthesize_dev would (exact matcher, one GPU); each wave's
     screen and fused kernel serve all K jobs at once (ia_synth_levels_batch), so the batch
-    costs about one job's per-wave launch latency.  Jobs of 3-channel pyramids (all of them:
-    a mix raises ValueError) go to synthesize3_batch_dev, where jobs given the same A and A'
-    pyramid tensors share one database per level (luminance jobs always build their own).
+    costs about one job's per-wave launch latency.  Jobs given the same A and A' pyramid
+    tensors (a DB group, db_groups: the runs of one A / A' pair in multi_main's batches) share
+    one algorithms.level_index per level: one database, one rotation and one rotated database,
+    built at the group's first job; workspaces and outputs stay per job.  With fewer groups than
+    jobs a level with a rotated database screens each wave in one k_screen16rs launch, which
+    reads a group's rows once for the query tiles of all its jobs (IA_SHARED_SCREEN=0: the K-job
+    k_screen16r); jobs with pyramids of their own are groups of one, and a batch of such jobs
+    makes the calls it always made.  Jobs of 3-channel pyramids (all of them: a mix raises
+    ValueError) go to synthesize3_batch_dev, which shares databases the same way.
     Returns one {level: (s, im[, debug])} dict per job."""
     K = len(jobs)
     if K == 0:
@@ -588,15 +594,22 @@ def synthesize_batch_dev(jobs, max_levels, k, weights, prof=False, debug=False, 
     w = weights if torch.is_tensor(weights) else _ia.to_dev(weights)
     levels = list(range(1, max_levels))
     calls = []          # level-major: calls[j * K + job]
-    # K databases per launch: fewer, longer chunks per database (the screen's workgroups
-    # amortise their prologue; c5: +11% on one box), restored before returning
+    group = db_groups(jobs)
+    # databases per launch: fewer, longer chunks per database (the screen's workgroups
+    # amortise their prologue; c5: +11% on one box), restored before returning.  A batch with
+    # shared databases sizes them by its K jobs too, not by its groups
     lib = _ia.lib()
     target = int(os.environ.get('IA_BATCH_CHUNKS', 0)) or max(64, 512 // K)
     prev = lib.ia_set_chunk_target(target)
     try:
         for level in levels:
-            for (A_pyr, Ap_list, B_pyr, Bp_pyr), kj in zip(jobs, ks):
-                index = algorithms.level_index(A_pyr, Ap_list, level, None, None)
+            # one index per DB group, built at the group's first job (an unshared batch makes
+            # its calls in the old order)
+            shared = {}
+            for q, ((A_pyr, Ap_list, B_pyr, Bp_pyr), kj) in enumerate(zip(jobs, ks)):
+                if group[q] not in shared:
+                    shared[group[q]] = algorithms.level_index(A_pyr, Ap_list, level, None, None)
+                index = shared[group[q]]
                 calls.append(_LevelCall(level, max_levels, index, B_pyr[level - 1], B_pyr[level],
                                         Bp_pyr[level - 1], Bp_pyr[level], w, kj, None, prof, False,
                                         debug))
@@ -662,7 +675,8 @@ def synthesize_jobs(jobs, max_levels, k, weights, rank=0, world=1, batch=0, prof
     multi_script.py:13-32): this rank synthesises jobs[j] for j in rank_jobs(len(jobs),
     rank, world), `batch` of them per set of launches (synthesize_batch_dev; 0 = all of this
     rank's jobs in one batch, 1 = one synthesize_dev call per job), one GPU per rank, no
-    collective.  jobs: the WHOLE job list, (A_pyr, Ap_pyr_list, B_pyr, Bp_pyr) device
+    collective.  Jobs of a batch given the same A and A' pyramid tensors share one database per
+    level (db_groups).  jobs: the WHOLE job list, (A_pyr, Ap_pyr_list, B_pyr, Bp_pyr) device
     pyramids per job (Bp_pyr updated in place); entries of other ranks' jobs are never read
     and may be None (or a callable returning the tuple, called only for this rank's jobs).
     k: one kappa or one per job (whole list).  Returns {j: {level: (s, im[, debug])}} for this
@@ -946,7 +960,8 @@ def _multi_batch(group, c, debug):
     runs that agree on _run_key are synthesised by one synthesize_batch_dev call, each with
     its own kappa, every other run alone; then each run's outputs as image_analogies_main
     writes them.  Batched runs of the same A and A' files share their A and A' pyramids
-    (_alias_pyramids), so a colour batch builds their databases once.  Returns {j: B' pyramid}."""
+    (_alias_pyramids), so a batch, luminance or colour, builds their databases once.
+    Returns {j: B' pyramid}."""
     import types
     ready = []
     for j, run in group:
@@ -999,9 +1014,10 @@ def multi_main(runs, c, debug=False, rank=None, world=None, batch=0):
     kappa; every other run goes alone.  Runs of one such call that name the same A and A'
     files under the same convert, remap_lum, AB_weight, levels and n_sm, and whose A and A'
     pyramids then are bit-equal (multi_script.py's 8 runs per material), share those pyramids:
-    a 3-channel batch builds one database and one rotated database per level for them and
-    screens their queries together (synthesize3_batch_dev); runs with other A / A' files join
-    the batch as DB groups of their own.  A batched run writes the same files with the same
+    the batch builds one database and one rotated database per level for them and screens
+    their queries together (synthesize_batch_dev, synthesize3_batch_dev); runs with other
+    A / A' files join the batch as DB groups of their own (so do runs under remap_lum, whose A
+    depends on B).  A batched run writes the same files with the same
     bytes as an unbatched one; on this path a run's overrides apply to that run only (each run
     takes a copy of `c`), while the unbatched loop sets them on `c` itself as before.
     Returns {j: B' pyramid} of this rank's runs."""

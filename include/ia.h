@@ -425,8 +425,23 @@ int ia_synth_levels(const IaSynthArgs *levels, int n, void *stream);
  * every job with its own inputs, DB, workspace and outputs.  Each wave of each level is ONE
  * screen launch and ONE fused-kernel launch for all K jobs (grid y = job), so K jobs cost
  * about one job's launch latency; results equal K separate ia_synth_levels calls.  Exact
- * matcher on one GPU only (comm and lsh NULL), 1 <= K <= 128. */
+ * matcher on one GPU only (comm and lsh NULL), 1 <= K <= 128.
+ * Jobs of a level may pass the same database (runs of one A / A' pair: the same rows at every
+ * level): they form a DB group (ia_batch_groups).  Two jobs of a level that pass the same non-null
+ * db, dbi or dbr must pass the same db, dbi, dbr, dbk, rot, center, amax, row0, nrows and src
+ * image pointers; otherwise the call returns IA_E_ARG, before anything is enqueued, with a
+ * message ending in "jobs sharing a database differ in <field>".  Nothing is written into those
+ * buffers during a synthesis.  With fewer groups than jobs the wave's screen of a level with a
+ * rotated DB is ONE k_screen16rs launch, which reads a group's rotated rows once for the query
+ * tiles of all its jobs; levels without one share the database and keep their launches; a batch
+ * without shared databases runs the launches it always ran.  Same results either way. */
 int ia_synth_levels_batch(const IaSynthArgs *levels, int n, int K, void *stream);
+/* the DB groups of one level's K jobs (level_jobs[0 .. K), 1 <= K <= 128), as
+ * ia_synth_levels_batch derives them: group_of_job[k] = the group of job k, groups numbered in
+ * job order; a job's database is its dbr where it has one, else its dbi, else its db, and two
+ * jobs are in one group when these are the same non-null pointer.  Returns the number of
+ * groups, or IA_E_ARG.  Pointer comparison on the host: no device call. */
+int ia_batch_groups(const IaSynthArgs *level_jobs, int K, int *group_of_job);
 /* after ia_synth_level(s) calls on `stream`: synchronises the stream and returns IA_E_SCHED if
  * a wait for a neighbouring pixel's decision inside the fused per-wave kernel timed out, or
  * IA_E_TIMEOUT if another rank's records on a device-side exchange never came: the results

@@ -144,6 +144,20 @@ int ia_diag_color16_stats(unsigned long long *out);
 int ia_diag_set_c3_shared_screen(int on);
 int ia_diag_screen3(const void *db3, long nrows, const double *q165, int M, double *e, double *eps,
                     double *qn);
+/* a luminance batch whose jobs share databases (ia_synth_levels_batch, ia_batch_groups) for this
+ * process (initially IA_SHARED_SCREEN, default 1): 1 one k_screen16rs launch per wave of a level
+ * with a rotated DB, 0 every job through the K-job k_screen16r as an unshared batch; same minima.
+ * -1 queries, other values leave it; returns the previous value.  Sampled when a level's call starts.
+ * ia_diag_shared_screen_waves: the waves whose screen was k_screen16rs since the library loaded.
+ * ia_diag_shared_screen_groups (host only): the query groups that launch forms for G DB groups of
+ * jobs_per_group[g] jobs (128 jobs at most) and M queries per job.  Returns their number and, if
+ * out is not NULL, writes IA_SHARED_QG_INTS ints per query group, in launch order: {DB group, first tile of
+ * the group's tile list, tiles, then for each of the 11 slots (job within the group, tile within the
+ * job), -1 -1 for a spare slot}.  IA_E_ARG on bad arguments. */
+#define IA_SHARED_QG_INTS 25
+int ia_diag_set_shared_screen(int on);
+long ia_diag_shared_screen_waves(void);
+int ia_diag_shared_screen_groups(const int *jobs_per_group, int G, int M, int *out);
 /* with IA_XW_TRACE=<level tag>: the fused kernel's phase stamps of that level (100 MHz
  * s_memrealtime) for waves < 4096 and the first 8 pixels of each, 12 stamps per pixel:
  * {start, ticket, e*, candidates, re-screen, rescore | coherence, winner, exchange,
