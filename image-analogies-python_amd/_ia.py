@@ -154,6 +154,10 @@ _SIGS = {
     'ia_sched_status': (ctypes.c_int, [ctypes.c_int]),
     'ia_synth_levels_batch': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.c_int, ctypes.c_int,
                                              _dp]),
+    'ia_synth_levels_lsh_batch': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.c_int, ctypes.c_int,
+                                                 _dp]),
+    'ia_synth_levels3_lsh_batch': (ctypes.c_int, [ctypes.POINTER(IaSynthArgs), ctypes.c_int, ctypes.c_int,
+                                                  _dp]),
     'ia_lsh_bytes': (ctypes.c_size_t, [ctypes.c_long, ctypes.c_int]),
     'ia_lsh_build': (ctypes.c_int, [ctypes.POINTER(IaSrcLevel), ctypes.c_long, ctypes.c_long, _dp,
                                     ctypes.POINTER(IaLsh), _dp]),

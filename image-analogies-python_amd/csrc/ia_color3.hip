@@ -1261,151 +1261,47 @@ template <bool TAIL>
 __global__ __launch_bounds__(256) void k_lsh3_pixel(Fin3 f, Lsh3View lv, const double *__restrict__ center,
                                                     long nrows, int qstride, int64_t *__restrict__ idx,
                                                     double *__restrict__ dist) {
-    __shared__ double qs[D3P], wsh[D3P];
-    __shared__ __attribute__((aligned(16))) float qc[D3P];
-    __shared__ unsigned int hk[LSH_MAXH];
-    __shared__ int lo_s[LSH_MAXH + 1], n_s[LSH_MAXH + 1];
-    __shared__ Acc8 acc[32 * 8];                // a pass's rows (32 x 8 parts)
-    __shared__ Acc8 cacc[15 * 8];               // the coherence rows
-    __shared__ double sump[15], sumw[15];
-    __shared__ long long rix[15];
-    __shared__ int rpos[15][3];
-    __shared__ double rd[4], rw[4];
-    __shared__ long long ri[4];
-    constexpr long long NONE = 0x7fffffffffffffffLL;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int m = blockIdx.x;
-    const int ro = tid >> 3, j = tid & 7;
-    const int y = f.y_lo + m, x = f.t - 3 * y;
-    // ---- one round trip: query, weights, coherence s / im
-    if (tid < D3P) {
-        const double q = tid < D3 ? f.q3[(long)m * qstride + tid] : 0.0;
-        qs[tid] = q;
-        wsh[tid] = TAIL && tid < D3 ? f.weights[tid] : 0.0;
-        qc[tid] = tid < D3 ? (float)(q - center[tid]) : 0.f;
-    }
-    if (TAIL && tid < 15) c3_window(tid, y, x, f, rix, rpos);
-    __syncthreads();
-    // ---- the hashes, one lane each
-    if (tid < lv.L * lv.k) {
-        const float4 *p4 = reinterpret_cast<const float4 *>(lv.proj + (long)tid * LSH3_PD);
-        const float4 *q4 = reinterpret_cast<const float4 *>(qc);
-        const float4 last = p4[D3 / 4];         // {p[164], b, 0, 0}
-        float d = last.y;
-#pragma unroll 8
-        for (int i = 0; i < D3 / 4; ++i) {
-            const float4 p = p4[i], a = q4[i];
-            d = fmaf(p.x, a.x, d);
-            d = fmaf(p.y, a.y, d);
-            d = fmaf(p.z, a.z, d);
-            d = fmaf(p.w, a.w, d);
-        }
-        d = fmaf(last.x, qc[D3 - 1], d);
-        hk[tid] = lsh_mix((int)floorf(d / lv.w), tid % lv.k);
-    }
-    __syncthreads();
-    // ---- per table: the bucket range, and the exclusive prefix of the candidate counts
-    if (wv == 0) {
-        int lo = 0, cnt = 0;
-        if (lane < lv.L) {
-            unsigned int key = 0;
-            for (int i = 0; i < lv.k; ++i) key += hk[lane * lv.k + i];
-            key &= (1u << lv.bits) - 1u;
-            const int *st = lv.start + (long)lane * ((1L << lv.bits) + 1);
-            long l = st[key], h = st[key + 1];
-            if (l == h) {   // empty bucket: take the neighbouring entries of the sorted table
-                l = l >= 2 ? l - 2 : 0;
-                h = l + 4 < nrows ? l + 4 : nrows;
-            }
-            lo = (int)l;
-            cnt = (int)(h - l > LSH_CAP ? LSH_CAP : h - l);
-        }
-        int inc = cnt;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
-        lo_s[lane] = lo;
-        n_s[lane] = inc - cnt;                  // (lanes >= L: the total)
-        if (lane == 63) n_s[LSH_MAXH] = inc;
-    }
-    __syncthreads();
-    const int total = n_s[LSH_MAXH];
-    const int npass = total > 32 ? (total + 31) / 32 : 1;
-    // ---- the candidates, 32 rows per pass (and, with the first, the coherence rows)
-    int tb = 0;
-    auto cand = [&](int c) -> long {            // the row of candidate c (-1: none)
-        if (c >= total) return -1;
-        while (n_s[tb + 1] <= c) ++tb;
-        const int lr = lv.rows[(long)tb * lv.npad + lo_s[tb] + (c - n_s[tb])];
-        return lr < nrows ? (long)lr : -1;
-    };
-    double bd = INFINITY, bw = 0.0;
-    long long bi = NONE;
-    long r = cand(ro);
-    for (int b = 0; b < npass; ++b) {
-        const long rn = b + 1 < npass ? cand(32 * (b + 1) + ro) : -1;
-        Acc8 ta{}, ca{};
-        if (r >= 0) ta = acc8_row(f.db3 + r * D3P, j, qs, wsh);
-        if (TAIL && b == 0 && tid < 15 * 8) {
-            const long long ix = rix[ro];
-            ca = acc8_row(f.db3 + (ix >= 0 ? ix : 0) * D3P, j, qs, wsh);
-        }
-        acc[tid] = ta;
-        if (TAIL && b == 0 && tid < 15 * 8) cacc[tid] = ca;
-        __syncthreads();
-        if (j == 0 && r >= 0) {
-            const double d = acc8_sum(acc + 8 * ro, false);
-            if (d < bd || (d == bd && r < bi)) {
-                bd = d;
-                bi = r;
-                const double sq = sqrt(acc8_sum(acc + 8 * ro, true));
-                bw = sq * sq;
-            }
-        }
-        if (TAIL && b == 0 && j == 0 && tid < 15 * 8) {
-            if (rix[ro] >= 0) {
-                sump[ro] = sqrt(acc8_sum(cacc + 8 * ro, false));
-                const double sq = sqrt(acc8_sum(cacc + 8 * ro, true));
-                sumw[ro] = sq * sq;
-            } else {
-                sump[ro] = INFINITY;
-                sumw[ro] = 0.0;
-            }
-        }
-        __syncthreads();   // acc is refilled by the next pass
-        r = rn;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(bd, o), ow = __shfl_xor(bw, o);
-        const long long oi = __shfl_xor(bi, o);
-        if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; bw = ow; }
-    }
-    if (lane == 0) { rd[wv] = bd; ri[wv] = bi; rw[wv] = bw; }
-    __syncthreads();
-    double wd = rd[0], ww = rw[0];
-    long long wi = ri[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-        if (rd[w] < wd || (rd[w] == wd && ri[w] < wi)) { wd = rd[w]; wi = ri[w]; ww = rw[w]; }
-    if (wi == NONE) {   // (workgroup-uniform) no valid candidate: row 0
-        if (tid < 8) acc[tid] = acc8_row(f.db3, tid, qs, wsh);
-        __syncthreads();
-        wi = 0;
-        wd = acc8_sum(acc, false);
-        const double sq = sqrt(acc8_sum(acc, true));
-        ww = sq * sq;
-    }
-    if constexpr (TAIL) {
-        if (wv != 0) return;
-        const long src = c3_decide(f, y, x, lane, wi, ww, sump, sumw, rix, rpos);
-        if (lane < 3) f.Bp_lg[((long)y * f.W + x) * 3 + lane] = f.Ap_lg[src + lane];
-    } else {
-        if (tid == 0) {
-            if (idx) idx[m] = wi;
-            if (dist) dist[m] = wd;
-        }
-    }
+#include "ia_color3_lsh.inc"
+}
+
+// ---- a batch of K identical-shape LSH jobs (ia_synth_levels3_lsh_batch) --------------------
+// One launch of k_query3b and one of k_lsh3_pixelb serve K jobs: the block's job is blockIdx.y,
+// and everything of job k comes from entry k of a device job table (one per level, in job 0's
+// workspace, where an exact batch keeps its C3Job table); the wave's scalars stay launch
+// arguments.  Jobs of one DB group pass the same rows, tables, projections and centre; neither
+// kernel writes into those, and everything written (q3, B', s, im, debug) stays per job.  Both
+// kernels wait for nothing, so the job dimension needs no forward-progress argument.
+struct L3Job {
+    Fin3 f;                        // t, y_lo: the launch's; q3: the job's query rows, read
+    double *q3;                    // the same rows, written by k_query3b
+    Lsh3View lv;
+    const double *center;
+    long nrows;
+    Img3 Bsm, Blg, Bpsm, Bplg;
+};
+__global__ __launch_bounds__(256) void k_query3b(const L3Job *__restrict__ jobs, int t, int y_lo) {
+    const L3Job &J = jobs[blockIdx.y];
+    const int m = blockIdx.x, k = threadIdx.x;
+    const int y = y_lo + m, x = t - 3 * y;
+    if (k >= D3P) return;
+    double v = 0.0;
+    if (k < D3_FULL) v = feat3(J.Bsm, J.Blg, y, x, k);
+    else if (k < D3) v = feat3(J.Bpsm, J.Bplg, y, x, k - D3_FULL);
+    J.q3[(long)m * D3P + k] = v;
+}
+__global__ __launch_bounds__(256) void k_lsh3_pixelb(const L3Job *__restrict__ jobs, int t, int y_lo) {
+    constexpr bool TAIL = true;
+    const L3Job &J = jobs[blockIdx.y];
+    Fin3 f = J.f;
+    f.t = t;
+    f.y_lo = y_lo;
+    const Lsh3View lv = J.lv;
+    const double *__restrict__ center = J.center;
+    const long nrows = J.nrows;
+    constexpr int qstride = D3P;
+    int64_t *const idx = nullptr;
+    double *const dist = nullptr;
+#include "ia_color3_lsh.inc"
 }
 
 // the replicated fp64 pyramids of a level's A side (feat3's inputs, as k_db3_build's)
@@ -1816,6 +1712,27 @@ struct Level3 {
                           J.nsk[b ^ 1], J.q16[b ^ 1], w.ctl, w.ctl + C3_CTL_ERR, w.dbox};
         return J;
     }
+    // a batch of K > 1 LSH jobs (ia_synth_levels3_lsh_batch, which has validated args[0..nj)):
+    // as init_batch, with the L3Job table in the place of the C3Job one (w.jtab's area)
+    bool lshb = false;
+    L3Job lsh_entry() const { return L3Job{f, w.q3, lv, a->center, a->nrows, Bsm, Blg, Bpsm, Bplg}; }
+    int init_lsh_batch(const IaSynthArgs *args, int nj, hipStream_t st, L3Job *pinned) {
+        static_assert(sizeof(L3Job) <= sizeof(C3Job), "the LSH job table lives in the jtab area");
+        int rc = init(&args[0], st);
+        if (rc) return rc;
+        IA_ARG(lsh && nj > 1 && nj <= IA_BATCH_MAX, "ia_synth_levels3_lsh_batch: bad batch");
+        K = nj;
+        lshb = true;
+        part.resize(K - 1);
+        pinned[0] = lsh_entry();
+        for (int k = 1; k < K; ++k) {
+            if ((rc = part[k - 1].init(&args[k], st))) return rc;
+            IA_ARG(part[k - 1].lsh, "ia_synth_levels3_lsh_batch: a job without lsh");
+            pinned[k] = part[k - 1].lsh_entry();
+        }
+        IA_HIP(hipMemcpyAsync(w.jtab, pinned, (size_t)K * sizeof(L3Job), hipMemcpyHostToDevice, st));
+        return IA_OK;
+    }
     // args[0..nj): the jobs' levels (validated by ia_synth_levels3_batch); the job table is
     // staged through `pinned` (kept alive by the caller until the copy has run)
     int init_batch(const IaSynthArgs *args, int nj, hipStream_t st, C3Job *pinned) {
@@ -1894,6 +1811,13 @@ struct Level3 {
         int y_lo, M;
         wave_rows(H, W, t, y_lo, M);
         if (M <= 0) return IA_OK;
+        if (lshb) {   // the single LSH job's two launches with the job as a grid dimension
+            const L3Job *jt = reinterpret_cast<const L3Job *>(w.jtab);
+            k_query3b<<<dim3(M, K), 256, 0, st>>>(jt, t, y_lo);
+            k_lsh3_pixelb<<<dim3(M, K), 256, 0, st>>>(jt, t, y_lo);
+            IA_LAUNCH_CHECK("ia_synth_levels3_lsh_batch wave");
+            return IA_OK;
+        }
         if (K > 1) return wave_batch(t, y_lo, M, st);
         f.t = t;
         f.y_lo = y_lo;
@@ -2255,9 +2179,75 @@ int ia_synth_levels3_batch(const IaSynthArgs *levels, int n, int K, void *stream
     IA_ARG(levels && n >= 1 && n <= 64, "ia_synth_levels3_batch: bad level count");
     for (size_t i = 0; i < (size_t)n * K; ++i)   // (batches shard by job, not by rows)
         IA_ARG(!levels[i].comm, "ia_synth_levels3_batch: a batch takes no comm (sharded levels: ia_synth_levels3)");
-    for (size_t i = 0; i < (size_t)n * K; ++i)   // (for any K: the LSH matcher has no batch form)
-        IA_ARG(!levels[i].lsh, "ia_synth_levels3_batch: a batch takes no lsh (LSH levels: ia_synth_levels3)");
+    for (size_t i = 0; i < (size_t)n * K; ++i)   // (for any K: LSH jobs have an entry of their own)
+        IA_ARG(!levels[i].lsh, "ia_synth_levels3_batch: a batch takes no lsh (LSH batches: ia_synth_levels3_lsh_batch)");
     return synth_levels3(levels, n, K, stream);
+}
+
+/* K LSH jobs per set of launches (k_query3b, k_lsh3_pixelb; K = 1: the single job's launches).
+ * Everything that cannot run is refused here, before anything is enqueued; the message names
+ * the field. */
+int ia_synth_levels3_lsh_batch(const IaSynthArgs *levels, int n, int K, void *stream) {
+    const std::string who = "ia_synth_levels3_lsh_batch";
+    IA_ARG(K >= 1 && K <= IA_BATCH_MAX, who + ": K out of range (1 .. 128)");
+    IA_ARG(levels && n >= 1 && n <= 64, who + ": bad level count");
+    for (int j = 0; j < n; ++j) {
+        const IaSynthArgs &a = levels[(size_t)j * K];
+        for (int k = 0; k < K; ++k) {
+            const IaSynthArgs &b = levels[(size_t)j * K + k];
+            IA_ARG(b.db && b.B_sm && b.B_lg && b.Bp_sm && b.Bp_lg && b.weights && b.s && b.im && b.workspace &&
+                       b.H > 0 && b.W > 0,
+                   who + ": bad args");
+            IA_ARG(b.lsh, who + ": every job of every level needs lsh (exact batches: ia_synth_levels3_batch)");
+            IA_ARG(!b.comm, who + ": an lsh batch takes no comm (the LSH matcher runs unsharded)");
+            IA_ARG(!b.dbg_px == !b.dbg_dist, who + ": debug outputs come in pairs (dbg_px, dbg_dist)");
+            {
+                const int rc = lsh3_level_check(b, who.c_str());   // center, tables
+                if (rc) return rc;
+            }
+            if (j > 0) {
+                const IaSynthArgs &c = levels[(size_t)(j - 1) * K + k];
+                IA_ARG(b.Bp_sm == c.Bp_lg && b.B_hs == c.H && b.B_ws == c.W,
+                       who + ": levels must be consecutive (level j's coarse B' = level j-1's B')");
+            }
+#define IA_SAME(field) IA_ARG(b.field == a.field, who + ": the jobs of an lsh batch differ in " #field)
+            IA_SAME(H); IA_SAME(W); IA_SAME(B_hs); IA_SAME(B_ws);
+            IA_SAME(src.Ah); IA_SAME(src.Aw); IA_SAME(src.A_hs); IA_SAME(src.A_ws); IA_SAME(src.nAp);
+            IA_SAME(nrows); IA_SAME(lsh->L); IA_SAME(lsh->k);
+#undef IA_SAME
+            IA_ARG(b.row0 == 0 && b.nrows == (long)b.src.nAp * b.src.Ah * b.src.Aw,
+                   who + ": an lsh batch takes no partial row range (row0, nrows)");
+            IA_ARG(!b.dbg_px == !a.dbg_px,
+                   who + ": the jobs of an lsh batch differ in having debug outputs (dbg_px, dbg_dist)");
+            // jobs passing one table set are one DB group: it stands for one database, so
+            // everything read with it is the same memory too
+            for (int p = 0; p < k; ++p) {
+                const IaSynthArgs &c = levels[(size_t)j * K + p];
+                if (c.lsh->mem != b.lsh->mem) continue;
+#define IA_SAME(field) IA_ARG(b.field == c.field, who + ": jobs sharing lsh->mem differ in " #field)
+                IA_SAME(lsh->proj); IA_SAME(lsh->w); IA_SAME(center); IA_SAME(db);
+                IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg);
+#undef IA_SAME
+                break;   // (p agrees with the group's earlier jobs already)
+            }
+        }
+    }
+    if (K == 1) return synth_levels3(levels, n, 1, stream);
+    hipStream_t st = S(stream);
+    int rc = g_pipe.begin(n, st);
+    if (rc) return rc;
+    // one job table per level, staged once through this thread's pinned buffer (ia_pipe.h)
+    L3Job *pinned = nullptr;
+    IA_HIP(g_pipe.staging((size_t)n * K * sizeof(L3Job), reinterpret_cast<void **>(&pinned)));
+    std::vector<Level3> run(n);
+    std::vector<PipeLevel> pl(n);
+    for (int j = 0; j < n; ++j) {
+        if ((rc = g_pipe.level_begin(j)) ||
+            (rc = run[j].init_lsh_batch(&levels[(size_t)j * K], K, g_pipe.stream(j), pinned + (size_t)j * K)))
+            return rc;
+        pl[j] = PipeLevel{run[j].H, run[j].W, false, false};
+    }
+    return pipe_execute(run, pl, 1, 0, st);
 }
 
 int ia_batch3_groups(const IaSynthArgs *level_jobs, int K, int *group_of_job) {

@@ -838,6 +838,36 @@ int launch_query_wave(const ImgPair &B, const ImgPair &Bp, int t, int y_lo, int 
     return IA_OK;
 }
 
+// The query rows of wave t for a batch of K LSH jobs (ia_synth_levels_lsh_batch): k_query_wave's
+// gather with the job as blockIdx.y and its images from the device job table.  Only q64 is
+// written: the LSH wave (k_lsh_query_b, k_lsh_tail_b) reads no other form of the query, so the
+// screen operands k_query_wave also leaves (qp, nq, q16) have no reader here.
+__global__ __launch_bounds__(64) void k_query_wave_lb(const LJob *__restrict__ jobs, int t, int y_lo) {
+    const LJob &J = jobs[blockIdx.y];
+    const int m = blockIdx.x;
+    const int y = y_lo + m, x = t - 3 * y;
+    const int lane = threadIdx.x;
+    const int hs = J.B_hs, ws = J.B_ws, h = J.H, w = J.W;
+    double v = 0.0;
+    if (lane < 55) {
+        const bool bp = lane >= 34;
+        const int e = bp ? lane - 34 : lane;
+        const bool coarse = e < 9;
+        const int tt = coarse ? e : e - 9;
+        const auto *sm = bp ? J.Bp_sm.p : J.B_sm.p;
+        const auto *lg = bp ? (decltype(J.B_lg.p))J.Bp_lg.p : J.B_lg.p;
+        v = coarse ? sm[(long)symi2((y >> 1) + tt / 3 - 1, hs) * ws + symi2((x >> 1) + tt % 3 - 1, ws)]
+                   : lg[(long)symi2(y + tt / 5 - 2, h) * w + symi2(x + tt % 5 - 2, w)];
+    }
+    if (lane < IA_DP) J.q64.p[(long)m * IA_DP + lane] = v;
+}
+
+int launch_query_wave_lsh_batch(const LJob *jobs, int K, int t, int y_lo, int M, hipStream_t st) {
+    k_query_wave_lb<<<dim3(M, K), 64, 0, st>>>(jobs, t, y_lo);
+    IA_LAUNCH_CHECK("k_query_wave_lb");
+    return IA_OK;
+}
+
 int launch_query_rows(const double *qin, int M, const double *center, float *qp, double *nq,
                       const float *amax, _Float16 *q16, hipStream_t st) {
     k_query_rows<<<M, 64, 0, st>>>(qin, M, center, qp, nq, amax, q16);

@@ -279,6 +279,45 @@ constexpr int IA_BATCH_MAX = 128;
 // groups, the jobs of each group, the jobs in group order
 constexpr int IA_GTAB_INTS = 1 + 2 * IA_BATCH_MAX;
 
+// one job of a batch of identical-shape LSH jobs (ia_synth_levels_lsh_batch): what its wave's
+// three launches (k_query_wave_lb, k_lsh_query_b, k_lsh_tail_b) read of it, job blockIdx.y's
+// from a device table of these in the place of the XJob table.  Jobs of one DB group hold the
+// same A / A' images, tables, projections and centre; nothing writes into those.
+struct LJob {
+    gptr<const double> A_sm, A_lg, Ap_sm, Ap_lg;   // DbSrc images (Ap: image 0)
+    int A_hs, A_ws, Ah, Aw;
+    gptr<const double> B_sm, B_lg, Bp_sm;
+    gptr<double> Bp_lg;
+    int B_hs, B_ws, H, W;
+    gptr<const int> start, rows;                    // the tables (ia_lsh_build)
+    gptr<const float> proj;
+    int L, k, bits;
+    float w;
+    long npad, row0, nrows, N_total;
+    gptr<const double> center;
+    gptr<double> q64;
+    gptr<Best> best;
+    gptr<unsigned long long> stats;                 // nullable (job 0 of a profiled level)
+    gptr<const double> weights;
+    double kappa_factor;
+    gptr<int32_t> s, im, dbg_px;
+    gptr<double> dbg_dist;
+    __host__ __device__ DbSrc src() const {
+        DbSrc d;
+        d.A = ImgPair{A_sm, A_lg, A_hs, A_ws, Ah, Aw};
+        d.Ap = ImgPair{Ap_sm, Ap_lg, A_hs, A_ws, Ah, Aw};
+        d.hw = (long)Ah * Aw;
+        d.hws = (long)A_hs * A_ws;
+        return d;
+    }
+    // wave t's view of the level state the per-pixel tail updates
+    __host__ __device__ FinishArgs finish(int t, int y_lo) const {
+        return FinishArgs{t, y_lo, W, N_total, weights, kappa_factor, Bp_lg, s, im, dbg_px, dbg_dist,
+                          nullptr, nullptr};
+    }
+};
+static_assert(sizeof(LJob) <= sizeof(XJob), "the LSH job table lives in the XJob table's area");
+
 // one launch of the fused per-wave kernel k_xwave (ia_xwave.hip): wave t's exact stage,
 // exchange (f.px) and per-pixel tail, and wave t + 1's query rows
 struct XArgs {
@@ -433,6 +472,14 @@ int launch_match(const DbSrc &src, long row0, long nrows, const void *db, const 
 int launch_lsh_match(const IaLsh *lsh, const DbSrc &src, long row0, long nrows, int M,
                      const double *q64, const double *center, Best *best,
                      unsigned long long *stats, hipStream_t st);
+// a batch of K LSH jobs (ia_synth_levels_lsh_batch), each launch with the job as blockIdx.y over
+// the device table `jobs`: the query rows q64 of wave t (ia_features.hip; the LSH wave reads no
+// other form of them), then best[M] per job (ia_lsh.hip)
+int launch_query_wave_lsh_batch(const LJob *jobs, int K, int t, int y_lo, int M, hipStream_t st);
+int launch_lsh_match_batch(const LJob *jobs, int K, int M, hipStream_t st);
+// IA_E_ARG unless lsh holds usable luminance tables' parameters (who: the caller's name)
+int lsh_check(const IaLsh *lsh, const char *who);
+void lsh_job_tables(const IaLsh *lsh, long nrows, LJob *J);
 
 // ---- the LSH definition's constants, shared by the luminance tables (ia_lsh.hip) and the
 // 165-dim ones (tables: ia_lsh.hip ia_lsh3_build; queries: ia_color3.hip k_lsh3_pixel)

@@ -140,66 +140,25 @@ __global__ __launch_bounds__(64) void k_lsh_query(DbSrc src, long row0, long nro
                                                   const double *__restrict__ center,
                                                   Best *__restrict__ best,
                                                   unsigned long long *stats) {
-    __shared__ double qs[IA_DP];
-    __shared__ float qc[IA_DP];
-    __shared__ unsigned int hk[LSH_MAXH];
-    __shared__ int lo_s[LSH_MAXH + 1], n_s[LSH_MAXH + 1];
-    const int q = blockIdx.x, lane = threadIdx.x;
-    if (lane < IA_DP) {
-        qs[lane] = q64[(long)q * IA_DP + lane];
-        qc[lane] = lane < IA_D ? (float)(qs[lane] - center[lane]) : 0.f;
-    }
-    __syncthreads();
-    if (lane < L * k) {
-        const float *p = proj + lane * IA_DP;
-        float d = p[55];
-        for (int e = 0; e < IA_D; ++e) d = fmaf(p[e], qc[e], d);
-        hk[lane] = lsh_mix((int)floorf(d / w), lane % k);
-    }
-    __syncthreads();
-    if (lane < L) {
-        unsigned int key = 0;
-        for (int i = 0; i < k; ++i) key += hk[lane * k + i];
-        key &= (1u << bits) - 1u;
-        const int *st = start + (long)lane * ((1L << bits) + 1);
-        long lo = st[key], hi = st[key + 1];
-        if (lo == hi) {   // empty bucket: take the neighbouring entries of the sorted table
-            lo = lo >= 2 ? lo - 2 : 0;
-            hi = lo + 4 < nrows ? lo + 4 : nrows;
-        }
-        lo_s[lane] = (int)lo;
-        n_s[lane] = (int)(hi - lo > LSH_CAP ? LSH_CAP : hi - lo);
-    }
-    __syncthreads();
-    if (lane == 0) {   // exclusive prefix of the per-table counts in n_s (in place)
-        int acc = 0;
-        for (int t = 0; t < L; ++t) { const int c = n_s[t]; n_s[t] = acc; acc += c; }
-        n_s[L] = acc;
-    }
-    __syncthreads();
-    const int total = n_s[L];
-    double bd = INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
-    int ncand = 0;
-    int t = 0;
-    for (int c = lane; c < total; c += 64) {   // candidates of all tables over the lanes
-        while (n_s[t + 1] <= c) ++t;
-        const int lr = rows[(long)t * npad + lo_s[t] + (c - n_s[t])];
-        if (lr < nrows) {
-            lbest(bd, bi, row_dist2(src, row0 + lr, qs), row0 + lr);
-            ++ncand;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(bd, o);
-        const long long oi = __shfl_xor(bi, o);
-        lbest(bd, bi, od, oi);
-        ncand += __shfl_xor(ncand, o);
-    }
-    if (lane == 0) {
-        best[q] = Best{bd, bi == 0x7fffffffffffffffLL ? row0 : bi};
-        if (stats) atomicAdd(&stats_slot(stats, q)[0], (unsigned long long)ncand);
-    }
+#include "ia_lsh_query.inc"
+}
+
+// a batch of K LSH jobs (ia_synth_levels_lsh_batch): the same query with the job as
+// blockIdx.y, everything of job k from entry k of the device job table
+__global__ __launch_bounds__(64) void k_lsh_query_b(const LJob *__restrict__ jobs) {
+    const LJob &J = jobs[blockIdx.y];
+    const DbSrc src = J.src();
+    const long row0 = J.row0, nrows = J.nrows, npad = J.npad;
+    const int bits = J.bits, L = J.L, k = J.k;
+    const float w = J.w;
+    const auto *__restrict__ start = J.start.p;
+    const auto *__restrict__ rows = J.rows.p;
+    const auto *__restrict__ proj = J.proj.p;
+    const auto *__restrict__ q64 = J.q64.p;
+    const auto *__restrict__ center = J.center.p;
+    auto *__restrict__ best = J.best.p;
+    unsigned long long *stats = J.stats;
+#include "ia_lsh_query.inc"
 }
 
 // device layout of IaLsh::mem: rows[L][npad] | start[L][2^bits + 1] | keys[L][npad] |
@@ -276,6 +235,33 @@ int launch_lsh_match(const IaLsh *lsh, const DbSrc &src, long row0, long nrows, 
                                   reinterpret_cast<const int *>(m + y.rows), lsh->proj, lsh->L,
                                   lsh->k, lsh->w, q64, center, best, stats);
     IA_LAUNCH_CHECK("k_lsh_query");
+    return IA_OK;
+}
+
+int lsh_check(const IaLsh *lsh, const char *who) {
+    IA_ARG(lsh->mem && lsh->proj, std::string(who) + ": lsh without tables (mem, proj)");
+    IA_ARG(lsh->L >= 1 && lsh->k >= 1 && lsh->L * lsh->k <= LSH_MAXH && lsh->w > 0.f,
+           std::string(who) + ": lsh needs 1 <= L*k <= 64 and w > 0");
+    return IA_OK;
+}
+
+// what a query reads of an ia_lsh_build table set, into a batch's job entry
+void lsh_job_tables(const IaLsh *lsh, long nrows, LJob *J) {
+    const LshLayout y = lsh_layout(nrows, lsh->L);
+    const char *m = reinterpret_cast<const char *>(lsh->mem);
+    J->start = reinterpret_cast<const int *>(m + y.start);
+    J->rows = reinterpret_cast<const int *>(m + y.rows);
+    J->proj = lsh->proj;
+    J->L = lsh->L;
+    J->k = lsh->k;
+    J->bits = lsh_bits(nrows);
+    J->w = lsh->w;
+    J->npad = db_rows_padded(nrows);
+}
+
+int launch_lsh_match_batch(const LJob *jobs, int K, int M, hipStream_t st) {
+    k_lsh_query_b<<<dim3(M, K), 64, 0, st>>>(jobs);
+    IA_LAUNCH_CHECK("k_lsh_query_b");
     return IA_OK;
 }
 

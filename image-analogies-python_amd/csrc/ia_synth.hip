@@ -165,6 +165,29 @@ __global__ __launch_bounds__(128) void k_lsh_tail(DbSrc src, const Best *__restr
     if (wv == 0) finish_apply(src, app, m, f, cs, d_app, lane);
 }
 
+// k_lsh_tail for a batch of K LSH jobs (ia_synth_levels_lsh_batch): the job is blockIdx.y,
+// its images, winners, query rows and level state come from the device job table; the wave's
+// t and y_lo stay launch arguments.  (A copy: the single-job kernel keeps its instructions.)
+__global__ __launch_bounds__(128) void k_lsh_tail_b(const LJob *__restrict__ jobs, int t, int y_lo) {
+    __shared__ double qs[IA_DP];
+    __shared__ CohSel cs;
+    const LJob &J = jobs[blockIdx.y];
+    const DbSrc src = J.src();
+    const FinishArgs f = J.finish(t, y_lo);
+    const int m = blockIdx.x;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x < IA_DP) qs[threadIdx.x] = J.q64.p[(long)m * IA_DP + threadIdx.x];
+    __syncthreads();
+    const long long app = J.best.p[m].idx;
+    if (wv == 1) {
+        const CohSel c = coh_pick(src, m, f, qs, lane);
+        if (lane == 0) cs = c;
+    }
+    const double d_app = wv == 0 ? app_wdist(src, app, f, qs, lane) : 0.0;
+    __syncthreads();
+    if (wv == 0) finish_apply(src, app, m, f, cs, d_app, lane);
+}
+
 // -------------------------------- workspace ----------------------------------------
 struct SynthWs {
     double *q64;
@@ -548,6 +571,7 @@ struct LevelRun {
         const int tail = plan.tail;
         if (tail == TAIL_SIM) return sim_wave(t, y_lo, M, sq);
         if (plan.xw) return xw_wave(t, y_lo, M, sq);
+        if (lshb) return lsh_wave_batch(t, y_lo, M, sq);
         if ((rc = launch_query_wave(B, Bp, t, y_lo, M, a->center, ws.q64, ws.qp, ws.nq, a->amax,
                                     ws.q16, sq)))
             return rc;
@@ -593,6 +617,56 @@ struct LevelRun {
             k_finish<<<M, 64, 0, sq>>>(src, ws.rec_all, ws.coh, nranks, M, fa);
         }
         IA_LAUNCH_CHECK("the unfused tail");
+        return IA_OK;
+    }
+
+    // ---- a batch of K > 1 LSH jobs (ia_synth_levels_lsh_batch, which has validated
+    // args[0..nj)): this run is job 0; the LJob table takes the XJob table's place in its
+    // workspace and is staged once per level through `pinned`
+    bool lshb = false;
+    LJob lsh_entry() const {
+        LJob J{};
+        J.A_sm = a->src.A_sm; J.A_lg = a->src.A_lg; J.Ap_sm = a->src.Ap_sm; J.Ap_lg = a->src.Ap_lg;
+        J.A_hs = a->src.A_hs; J.A_ws = a->src.A_ws; J.Ah = a->src.Ah; J.Aw = a->src.Aw;
+        J.B_sm = a->B_sm; J.B_lg = a->B_lg; J.Bp_sm = a->Bp_sm; J.Bp_lg = a->Bp_lg;
+        J.B_hs = a->B_hs; J.B_ws = a->B_ws; J.H = H; J.W = W;
+        lsh_job_tables(a->lsh, a->nrows, &J);
+        J.row0 = a->row0; J.nrows = a->nrows; J.N_total = a->N_total;
+        J.center = a->center; J.q64 = ws.q64; J.best = ws.best_local;
+        J.stats = prof ? ws.stats : nullptr;
+        J.weights = a->weights; J.kappa_factor = a->kappa_factor;
+        J.s = a->s; J.im = a->im; J.dbg_px = a->dbg_px; J.dbg_dist = a->dbg_dist;
+        return J;
+    }
+    int init_lsh_batch(const IaSynthArgs *args, int nj, hipStream_t st, LJob *pinned) {
+        int rc = init(&args[0], st, nj);
+        if (rc) return rc;
+        IA_ARG(plan.tail == TAIL_LSH && nj > 1 && nj <= IA_BATCH_MAX, "ia_synth_levels_lsh_batch: bad batch");
+        lshb = true;
+        part.resize(K - 1);
+        pinned[0] = lsh_entry();
+        for (int k = 1; k < K; ++k) {
+            part[k - 1].member = true;
+            if ((rc = part[k - 1].init(&args[k], st, K))) return rc;
+            IA_ARG(part[k - 1].plan.tail == TAIL_LSH, "ia_synth_levels_lsh_batch: a job without lsh");
+            pinned[k] = part[k - 1].lsh_entry();
+        }
+        IA_HIP(hipMemcpyAsync(ws.jtab, pinned, (size_t)K * sizeof(LJob), hipMemcpyHostToDevice, st));
+        return IA_OK;
+    }
+    // wave t of an LSH batch: the single job's three launches with the job as a grid dimension
+    // (the events bracket the LSH query kernel, as for one job)
+    int lsh_wave_batch(int t, int y_lo, int M, hipStream_t sq) {
+        const LJob *jt = reinterpret_cast<const LJob *>(ws.jtab);
+        int rc;
+        if ((rc = launch_query_wave_lsh_batch(jt, K, t, y_lo, M, sq))) return rc;
+        hipEvent_t e0 = wave_event(0), e1 = wave_event(1);
+        if (e0) IA_HIP(hipEventRecord(e0, sq));
+        if ((rc = launch_lsh_match_batch(jt, K, M, sq))) return rc;
+        if (e1) IA_HIP(hipEventRecord(e1, sq));
+        if ((rc = wave_counted(t, M, sq))) return rc;
+        k_lsh_tail_b<<<dim3(M, K), 128, 0, sq>>>(jt, t, y_lo);
+        IA_LAUNCH_CHECK("k_lsh_tail_b");
         return IA_OK;
     }
 
@@ -1157,6 +1231,70 @@ int ia_synth_levels_batch(const IaSynthArgs *levels, int n, int K, void *stream)
             }
         }
     return synth_levels(levels, n, K, stream);
+}
+
+/* K LSH jobs per set of launches (k_query_wave_lb, k_lsh_query_b, k_lsh_tail_b; K = 1: the
+ * single job's launches).  Everything that cannot run is refused here, before anything is
+ * enqueued; the message names the field. */
+int ia_synth_levels_lsh_batch(const IaSynthArgs *levels, int n, int K, void *stream) {
+    const std::string who = "ia_synth_levels_lsh_batch";
+    IA_ARG(K >= 1 && K <= IA_BATCH_MAX, who + ": K out of range (1 .. 128)");
+    IA_ARG(levels && n >= 1 && n <= 64, who + ": bad level count");
+    for (int j = 0; j < n; ++j) {
+        const IaSynthArgs &a = levels[(size_t)j * K];
+        for (int k = 0; k < K; ++k) {
+            const IaSynthArgs &b = levels[(size_t)j * K + k];
+            IA_ARG(b.lsh, who + ": every job of every level needs lsh (exact batches: ia_synth_levels_batch)");
+            IA_ARG(b.center, who + ": lsh needs center (55 doubles)");
+            IA_ARG(!b.comm, who + ": an lsh batch takes no comm (the LSH matcher runs unsharded)");
+#define IA_SAME(field) IA_ARG(b.field == a.field, who + ": the jobs of an lsh batch differ in " #field)
+            IA_SAME(H); IA_SAME(W); IA_SAME(B_hs); IA_SAME(B_ws);
+            IA_SAME(src.Ah); IA_SAME(src.Aw); IA_SAME(src.A_hs); IA_SAME(src.A_ws); IA_SAME(src.nAp);
+            IA_SAME(nrows); IA_SAME(lsh->L); IA_SAME(lsh->k);
+#undef IA_SAME
+            {
+                int rc = check_args(&b);
+                if (rc || (rc = lsh_check(b.lsh, who.c_str()))) return rc;
+            }
+            if (j > 0) {
+                const IaSynthArgs &c = levels[(size_t)(j - 1) * K + k];
+                IA_ARG(b.Bp_sm == c.Bp_lg && b.B_hs == c.H && b.B_ws == c.W,
+                       who + ": levels must be consecutive (level j's coarse B' = level j-1's B')");
+            }
+            IA_ARG(b.row0 == 0 && b.nrows == b.N_total,
+                   who + ": an lsh batch takes no partial row range (row0, nrows)");
+            IA_ARG(!b.dbg_px == !a.dbg_px,
+                   who + ": the jobs of an lsh batch differ in having debug outputs (dbg_px, dbg_dist)");
+            // jobs passing one table set are one DB group: it stands for one level index, so
+            // everything read with it is the same memory too
+            for (int p = 0; p < k; ++p) {
+                const IaSynthArgs &c = levels[(size_t)j * K + p];
+                if (c.lsh->mem != b.lsh->mem) continue;
+#define IA_SAME(field) IA_ARG(b.field == c.field, who + ": jobs sharing lsh->mem differ in " #field)
+                IA_SAME(lsh->proj); IA_SAME(lsh->w); IA_SAME(center);
+                IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg);
+#undef IA_SAME
+                break;   // (p agrees with the group's earlier jobs already)
+            }
+        }
+    }
+    if (K == 1) return synth_levels(levels, n, 1, stream);
+    hipStream_t st = S(stream);
+    int rc = g_pipe.begin(n, st);
+    if (rc) return rc;
+    // one job table per level, staged once through this thread's pinned buffer (ia_pipe.h)
+    LJob *pinned = nullptr;
+    IA_HIP(g_pipe.staging((size_t)n * K * sizeof(LJob), reinterpret_cast<void **>(&pinned)));
+    std::vector<LevelRun> run(n);
+    std::vector<PipeLevel> pl(n);
+    for (int j = 0; j < n; ++j) {
+        if ((rc = g_pipe.level_begin(j)) ||
+            (rc = run[j].init_lsh_batch(&levels[(size_t)j * K], K, g_pipe.stream(j), pinned + (size_t)j * K)))
+            return rc;
+        pl[j] = PipeLevel{run[j].H, run[j].W, false, false};
+    }
+    static const int order = env_int("IA_PIPE_ORDER", 0);
+    return pipe_execute(run, pl, order, pipe_ahead(), st);
 }
 
 int ia_batch_groups(const IaSynthArgs *level_jobs, int K, int *group_of_job) {

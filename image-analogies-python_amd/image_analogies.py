@@ -390,7 +390,8 @@ def rot3_batch_shared():
     return os.environ.get('IA_ROT3_BATCH_SHARED', '1') != '0'
 
 
-def synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=False, check=True, rot_shared=None):
+def synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=False, check=True, rot_shared=None,
+                          lsh=None):
     """K 3-channel analogies of identical shapes in ONE set of launches per wave
     (ia_synth_levels3_batch: k_screen3r and the fused k_exact3<true> with the job as a grid
     dimension).  Per DB group and level one database (ia_db3_build) and one rotated database
@@ -405,11 +406,26 @@ def synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=False, check=True
     matcher exact, so the results are those of synthesize3_dev per job either way.  The batch form
     exists for the rotated screen only: with IA_DB_ROT=0 or the exhaustive search
     (IA_COLOR16=0) the jobs run one after the other through synthesize3_dev.  jobs, ks, the
-    return value: as synthesize_batch_dev."""
+    return value: as synthesize_batch_dev.
+    lsh: None, or the build_lsh arguments (one set for the batch): every job then runs the
+    approximate LSH matcher as synthesize3_dev(lsh=...) does, K jobs per launch
+    (ia_synth_levels3_lsh_batch: k_query3b and k_lsh3_pixelb with the job as a grid dimension).
+    Per DB group and level one database and one set of tables (algorithms.lsh3_tables), built at
+    the group's first job; every job of the group points at them and at their centre; no rotation
+    and no rotated database is built.  The results are synthesize3_dev(lsh=...)'s per job."""
     lib = _ia.lib()
     st = _ia.stream()
     K = len(jobs)
     weights = weights if torch.is_tensor(weights) else _ia.to_dev(weights)
+    if lsh is not None:
+        if max_levels <= 1:
+            return [{} for _ in jobs]
+        arr, res, keep = _batch3_lsh_args(jobs, max_levels, ks, weights, debug, lsh)
+        _ia.check(lib.ia_synth_levels3_lsh_batch(arr, max_levels - 1, K, st), 'ia_synth_levels3_lsh_batch')
+        if check:
+            _ia.check(lib.ia_synth3_status(arr, len(arr), st), 'ia_synth3_status')
+        del keep
+        return res
     if K == 1 or not _ia.db_rot_enabled() or lib.ia_diag_set_color16(-1) == 0:
         return [synthesize3_dev(A_pyr, Ap_list, B_pyr, Bp_pyr, max_levels, kj, weights, debug=debug)
                 for (A_pyr, Ap_list, B_pyr, Bp_pyr), kj in zip(jobs, ks)]
@@ -463,6 +479,28 @@ def _batch3_args(jobs, max_levels, ks, weights, debug, rot_shared):
                 dbrs[g] = algorithms.rot3_apply(db3, N, rot)
             a, (s, im, dbg), bufs = _level3_args(built[g][level], rot, dbrs[g], B_pyr, Bp_pyr, level,
                                                  max_levels, kj, weights, debug)
+            args.append(a)
+            keep.append(bufs)
+            res[q][level] = (s, im) if dbg is None else (s, im, dbg)
+    return (_ia.IaSynthArgs * len(args))(*args), res, keep
+
+
+def _batch3_lsh_args(jobs, max_levels, ks, weights, debug, lsh):
+    """_batch3_args for an LSH batch (ia_synth_levels3_lsh_batch): one database and one set of
+    LSH tables per DB group and level, built at the group's first job; no rotated database."""
+    group = db_groups(jobs)
+    args, keep, res = [], [], [{} for _ in jobs]
+    for level in range(1, max_levels):
+        shared = {}
+        keep.append(shared)
+        for q, ((A_pyr, Ap_list, B_pyr, Bp_pyr), kj) in enumerate(zip(jobs, ks)):
+            if group[q] not in shared:
+                built = _db3_level(A_pyr, Ap_list, level)
+                shared[group[q]] = (built, algorithms.lsh3_tables(built[1], built[3], built[6], built[5], **lsh))
+            built, tabs = shared[group[q]]
+            a, (s, im, dbg), bufs = _level3_args(built, None, None, B_pyr, Bp_pyr, level, max_levels, kj,
+                                                 weights, debug)
+            a.lsh, a.center = ctypes.pointer(tabs[0]), _ia.ptr(tabs[1]).value
             args.append(a)
             keep.append(bufs)
             res[q][level] = (s, im) if dbg is None else (s, im, dbg)
@@ -565,7 +603,7 @@ def synthesize_dev(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, max_levels, k, weights,
     return out
 
 
-def synthesize_batch_dev(jobs, max_levels, k, weights, prof=False, debug=False, check=True):
+def synthesize_batch_dev(jobs, max_levels, k, weights, prof=False, debug=False, check=True, lsh=None):
     """K independent analogies of identical shapes in ONE set of launches per wave (the
     multi_script batch, multi_script.py:13-32: each run an image_analogies_main of its own;
     SURVEY §8(e) config 5).  jobs: list of (A_pyr, Ap_pyr_list, B_pyr, Bp_pyr) device
@@ -581,6 +619,12 @@ def synthesize_batch_dev(jobs, max_levels, k, weights, prof=False, debug=False, 
     k_screen16r); jobs with pyramids of their own are groups of one, and a batch of such jobs
     makes the calls it always made.  Jobs of 3-channel pyramids (all of them: a mix raises
     ValueError) go to synthesize3_batch_dev, which shares databases the same way.
+    lsh: None (the exact matcher, everything above), or the build_lsh arguments (one set for the
+    batch): every job then runs the approximate LSH matcher as synthesize_dev(lsh=...) does, K
+    jobs per launch (ia_synth_levels_lsh_batch: the query rows, the LSH query and the LSH tail
+    with the job as a grid dimension); a DB group shares one algorithms.level_index(..., lsh=lsh)
+    per level, tables and centre included, built at its first job.  The results are
+    synthesize_dev(lsh=...)'s per job.
     Returns one {level: (s, im[, debug])} dict per job."""
     K = len(jobs)
     if K == 0:
@@ -590,11 +634,31 @@ def synthesize_batch_dev(jobs, max_levels, k, weights, prof=False, debug=False, 
     if any(colour):
         if not all(colour):
             raise ValueError('synthesize_batch_dev: a batch is all 3-channel or all luminance jobs')
+        if lsh is not None:
+            return synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=debug, check=check, lsh=lsh)
         return synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=debug, check=check)
     w = weights if torch.is_tensor(weights) else _ia.to_dev(weights)
     levels = list(range(1, max_levels))
     calls = []          # level-major: calls[j * K + job]
     group = db_groups(jobs)
+    if lsh is not None:
+        # (no chunk target of the batch's own: the tables' padding follows the target they were
+        # built under, and the LSH wave reads no chunked database)
+        if not levels:
+            return [{} for _ in jobs]
+        for level in levels:
+            shared = {}
+            for q, ((A_pyr, Ap_list, B_pyr, Bp_pyr), kj) in enumerate(zip(jobs, ks)):
+                if group[q] not in shared:
+                    shared[group[q]] = algorithms.level_index(A_pyr, Ap_list, level, None, lsh)
+                calls.append(_LevelCall(level, max_levels, shared[group[q]], B_pyr[level - 1], B_pyr[level],
+                                        Bp_pyr[level - 1], Bp_pyr[level], w, kj, None, prof, False, debug))
+        arr = (_ia.IaSynthArgs * len(calls))(*[c.args for c in calls])
+        _ia.check(_ia.lib().ia_synth_levels_lsh_batch(arr, len(levels), K, _ia.stream()),
+                  'ia_synth_levels_lsh_batch')
+        if check:
+            _ia.check(_ia.lib().ia_synth_status(arr, len(calls), _ia.stream()), 'ia_synth_status')
+        return [{level: calls[j * K + q].result() for j, level in enumerate(levels)} for q in range(K)]
     # databases per launch: fewer, longer chunks per database (the screen's workgroups
     # amortise their prologue; c5: +11% on one box), restored before returning.  A batch with
     # shared databases sizes them by its K jobs too, not by its groups
@@ -670,7 +734,7 @@ def release_exchanges(comms):
 
 
 def synthesize_jobs(jobs, max_levels, k, weights, rank=0, world=1, batch=0, prof=False,
-                    debug=False, check=True):
+                    debug=False, check=True, lsh=None):
     """Independent analogies of identical shapes spread over ranks (SURVEY §8(e) config 5,
     multi_script.py:13-32): this rank synthesises jobs[j] for j in rank_jobs(len(jobs),
     rank, world), `batch` of them per set of launches (synthesize_batch_dev; 0 = all of this
@@ -679,24 +743,26 @@ def synthesize_jobs(jobs, max_levels, k, weights, rank=0, world=1, batch=0, prof
     level (db_groups).  jobs: the WHOLE job list, (A_pyr, Ap_pyr_list, B_pyr, Bp_pyr) device
     pyramids per job (Bp_pyr updated in place); entries of other ranks' jobs are never read
     and may be None (or a callable returning the tuple, called only for this rank's jobs).
-    k: one kappa or one per job (whole list).  Returns {j: {level: (s, im[, debug])}} for this
-    rank's jobs."""
+    k: one kappa or one per job (whole list).  lsh: None, or the build_lsh arguments: every job
+    runs the LSH matcher (synthesize_dev / synthesize_batch_dev with that lsh).  Returns
+    {j: {level: (s, im[, debug])}} for this rank's jobs."""
     mine = rank_jobs(len(jobs), rank, world)
     ks = list(k) if isinstance(k, (list, tuple)) else [k] * len(jobs)
     if len(ks) != len(jobs):
         raise ValueError('synthesize_jobs: %d kappas for %d jobs' % (len(ks), len(jobs)))
     step = batch if batch and batch > 0 else max(1, len(mine))
     out = {}
+    extra = {} if lsh is None else {'lsh': lsh}
     for g0 in range(0, len(mine), step):
         group = mine[g0:g0 + step]
         ins = [jobs[j]() if callable(jobs[j]) else jobs[j] for j in group]
         if len(group) == 1:
             A_pyr, Ap_list, B_pyr, Bp_pyr = ins[0]
             res = [synthesize_dev(A_pyr, Ap_list, B_pyr, Bp_pyr, max_levels, ks[group[0]], weights,
-                                  prof=prof, debug=debug, check=check)]
+                                  prof=prof, debug=debug, check=check, **extra)]
         else:
             res = synthesize_batch_dev(ins, max_levels, [ks[j] for j in group], weights, prof=prof,
-                                       debug=debug, check=check)
+                                       debug=debug, check=check, **extra)
         out.update(zip(group, res))
     return out
 
@@ -930,9 +996,24 @@ def write_outputs(res, Bp_pyr, color_pyr_list, c, out_path, debug=False, outputs
 
 def _run_key(c, A_pyr, Ap_pyr_list, B_pyr):
     """What the runs of one batch agree on (multi_main): channel count, levels, every pyramid
-    shape, the number of A' images, the exact matcher."""
+    shape, the number of A' images, and the matcher: None for the exact one, else the LSH
+    parameter set (tables, hashes, width, seed) as a hashable, on which runs agree exactly."""
     shapes = tuple(tuple(p.shape) for pyr in (A_pyr, B_pyr) for p in pyr)
-    return (c.num_ch, c.max_levels, shapes, len(Ap_pyr_list), algorithms.lsh_params(c) is None)
+    lsh = algorithms.lsh_params(c)
+    return (c.num_ch, c.max_levels, shapes, len(Ap_pyr_list),
+            None if lsh is None else tuple(sorted(lsh.items())))
+
+
+# the default of IA_LSH_BATCH per row type (3-channel, luminance): set by the measurement of
+# profiles/lsh_batch_ab.txt (DESIGN.md §3b, §3c)
+LSH_BATCH_DEFAULT = {True: 1, False: 1}
+
+
+def lsh_batch_enabled(colour):
+    """Whether multi_main's batches send LSH runs through synthesize_batch_dev(lsh=...)
+    (IA_LSH_BATCH: 1 yes, 0 one synthesize_dev call per run; unset: the row type's default)."""
+    v = os.environ.get('IA_LSH_BATCH')
+    return (v != '0') if v is not None else bool(LSH_BATCH_DEFAULT[bool(colour)])
 
 
 def _alias_pyramids(same):
@@ -957,7 +1038,8 @@ def _alias_pyramids(same):
 def _multi_batch(group, c, debug):
     """multi_main's batched path for the runs `group` ([(j, run)], at most `batch` of them):
     each run is set up under its own copy of the config (its overrides apply to it alone);
-    runs that agree on _run_key are synthesised by one synthesize_batch_dev call, each with
+    runs that agree on _run_key (exact runs, or LSH runs of one parameter set unless
+    IA_LSH_BATCH=0) are synthesised by one synthesize_batch_dev call, each with
     its own kappa, every other run alone; then each run's outputs as image_analogies_main
     writes them.  Batched runs of the same A and A' files share their A and A' pyramids
     (_alias_pyramids), so a batch, luminance or colour, builds their databases once.
@@ -984,10 +1066,11 @@ def _multi_batch(group, c, debug):
         same = [r for r in ready if r[4] == key]
         c0 = same[0][2]
         weights = _ia.to_dev(c0.weights)
-        if len(same) > 1 and key[4]:
+        lsh = algorithms.lsh_params(c0)
+        if len(same) > 1 and (lsh is None or lsh_batch_enabled(same[0][3][2][-1].dim() == 3)):
             _alias_pyramids(same)
             res = synthesize_batch_dev([r[3][:4] for r in same], c0.max_levels, [r[2].k for r in same],
-                                       weights, debug=debug)
+                                       weights, debug=debug, **({} if lsh is None else {'lsh': lsh}))
         else:
             res = [synthesize_dev(*r[3][:4], r[2].max_levels, r[2].k, weights,
                                   lsh=algorithms.lsh_params(r[2]), debug=debug) for r in same]
@@ -1009,9 +1092,12 @@ def multi_main(runs, c, debug=False, rank=None, world=None, batch=0):
     out_path[, overrides]) tuples; overrides is a dict of config fields set on `c` before
     the run (multi_script.py:31 sets c.k so).  batch = K > 1: this rank's runs are set up in
     order in groups of at most K, and the runs of a group that agree on the channel count,
-    max_levels, every pyramid shape, the number of A' images and the exact matcher are
+    max_levels, every pyramid shape, the number of A' images and the matcher (the exact one, or
+    c.matcher = 'lsh' with the same tables, hashes, width and seed) are
     synthesised by ONE synthesize_batch_dev call (luminance or 3-channel), each with its own
-    kappa; every other run goes alone.  Runs of one such call that name the same A and A'
+    kappa; every other run goes alone.  LSH runs of one such call share one set of LSH tables
+    per level where they share their A and A' pyramids; IA_LSH_BATCH=0 sends LSH runs one by one
+    through synthesize_dev as before.  Runs of one such call that name the same A and A'
     files under the same convert, remap_lum, AB_weight, levels and n_sm, and whose A and A'
     pyramids then are bit-equal (multi_script.py's 8 runs per material), share those pyramids:
     the batch builds one database and one rotated database per level for them and screens

@@ -436,6 +436,25 @@ int ia_synth_levels(const IaSynthArgs *levels, int n, void *stream);
  * tiles of all its jobs; levels without one share the database and keep their launches; a batch
  * without shared databases runs the launches it always ran.  Same results either way. */
 int ia_synth_levels_batch(const IaSynthArgs *levels, int n, int K, void *stream);
+/* K LSH jobs of identical shapes (every level of every job with lsh and center), level-major as
+ * above: each wave of each level is ONE launch each of the query rows, the LSH query and the
+ * LSH tail for all K jobs (grid y = job; job k's images, tables, projections, centre, buffers
+ * and outputs come from a device job table staged once per level).  Results equal K separate
+ * ia_synth_levels calls, bit for bit; ia_synth_status takes all n * K args.  1 <= K <= 128;
+ * K = 1 makes ia_synth_levels' launches.  Jobs of a level may pass the same lsh->mem (one table
+ * set per A / A' pair): they must then pass the same lsh->proj, lsh->w, center and src image
+ * pointers.  IA_E_ARG before anything is enqueued, the field named in ia_last_error(), when a
+ * job of a level has no lsh or no center, carries a comm or a partial row range, when the jobs
+ * of a level differ in a shape, in lsh->L or lsh->k or in having debug outputs, when jobs sharing
+ * lsh->mem differ in one of the above, and when the table parameters cannot run (mem, proj,
+ * 1 <= L k <= 64, w > 0).  The tables' padding follows the calling thread's chunk target
+ * (ia_set_chunk_target): call under the target ia_lsh_build ran under. */
+int ia_synth_levels_lsh_batch(const IaSynthArgs *levels, int n, int K, void *stream);
+/* the same for 3-channel levels (tables of ia_lsh3_build, center of 165 doubles; a wave is ONE
+ * k_query3b and ONE k_lsh3_pixelb launch for all K jobs); jobs sharing lsh->mem must pass the
+ * same db too, and proj must be 16-byte aligned.  K = 1 makes ia_synth_levels3's launches;
+ * ia_synth3_status takes all n * K args. */
+int ia_synth_levels3_lsh_batch(const IaSynthArgs *levels, int n, int K, void *stream);
 /* the DB groups of one level's K jobs (level_jobs[0 .. K), 1 <= K <= 128), as
  * ia_synth_levels_batch derives them: group_of_job[k] = the group of job k, groups numbered in
  * job order; a job's database is its dbr where it has one, else its dbi, else its db, and two
