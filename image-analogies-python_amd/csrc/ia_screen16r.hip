@@ -11,12 +11,13 @@
 //
 // The screen's structure is the row form's of ia_screen16.hip (k_screen16): queries are the
 // stationary MFMA B operand (half8 per query block and lane); the DB streams through LDS in
-// 4-tile stages (16 KiB at P = 3, global_load_lds_dwordx4, non-temporal, a ring of 3 buffers,
+// 4-tile stages (16 KiB at P = 3, global_load_lds_dwordx4, non-temporal, a ring of 2 buffers,
 // one LDS-only barrier per stage) and every byte fetched feeds the block's 4 waves; the
 // stage's (query block, row block) chains are cut into 4 equal runs (chain balance), each
 // chain's MFMAs run back to back and its running-minimum fold is taken a few chains later
 // (no MFMA -> VALU hazard pads), interleaved with the later chains' MFMAs; minima staged in
-// LDS 8 segments at a time.
+// LDS 2 segments at a time (the compact form: 8, a whole part of the finest levels, so that a
+// query's minima leave in runs of 32 B).
 #include "ia_internal.h"
 #include "ia_rot16.h"
 #include "../../include/ia_diag.h"
@@ -55,6 +56,28 @@ constexpr int R16_RING = IA_R16_RING;
 #define IA_R16_SPC 2
 #endif
 constexpr int SPC_STAGE = IA_R16_SPC;   // segments of minima staged in LDS at a time
+// The compact form (k_screen16c) has its own stage geometry (DESIGN.md §4d "compact"): tiles per
+// stage (4 or 8: 8 or 16 KiB; a level whose segments are no whole number of 8-tile stages takes
+// 4), stage buffers, segments of minima staged at a time, blocks per CU (A/B builds).  Measured
+// on c4: deeper rings move nothing (the launch is not bound by the stream's latency); staging 8
+// segments (11 KiB at G = 11) cuts the launch's HBM writes from 40.2 to 11.2 MB (2 segments leave
+// as 8-byte pieces of 32-byte sectors) and is what ships.  Only the values below are built and
+// tested by the suite; the others are lab settings
+#ifndef IA_RK_TILES
+#define IA_RK_TILES 4
+#endif
+#ifndef IA_RK_RING
+#define IA_RK_RING 2
+#endif
+#ifndef IA_RK_SPC
+#define IA_RK_SPC 8
+#endif
+#ifndef IA_RK_OCC
+#define IA_RK_OCC 4
+#endif
+constexpr int RK_TILES = IA_RK_TILES, RK_RING = IA_RK_RING, RK_SPC = IA_RK_SPC;
+static_assert(RK_TILES == 4 || RK_TILES == 8, "a compact stage is one or two 128-row stages of the stage map");
+static_assert(RK_RING >= 2 && R16_RING >= 2 && RK_SPC >= 1 && RK_SPC <= 16, "stage ring, staged minima");
 
 // chain balance (as ia_screen16.hip): the 4G chains of a stage in the order 4t + u cut into
 // 4 equal runs of G, one per wave
@@ -346,12 +369,12 @@ __device__ __forceinline__ void r16_close(int s, int tps, int *smin, float (&mn)
         }
     }
 }
-template <int G, int W, int NS>
+template <int G, int W, int NS, int TILES = STAGE_TILES, int SPC = SPC_STAGE>
 __device__ __forceinline__ void r16_close_s16(int s, int tps, int *smin, float (&mn)[NS], int lane) {
     constexpr int T0 = c16_t0<G, W>();
-    const int done = (s + 1) * STAGE_TILES;
+    const int done = (s + 1) * TILES;
     if (done % tps == 0) {
-        int *sm = smin + ((done / tps - 1) % SPC_STAGE) * (G * 32);
+        int *sm = smin + ((done / tps - 1) % SPC) * (G * 32);
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             float m = fminf(mn[k], __shfl_xor(mn[k], 16));
@@ -372,22 +395,41 @@ __device__ __forceinline__ void stage_barrier() {
 }
 
 // The DB stream needs ~60 KB in flight per CU to keep the MFMA pipe fed at HBM latency
-// (11.6 B per cycle and CU at full rate), so stages land in a ring of R16_RING buffers,
-// R16_RING - 1 stages ahead (2 blocks per CU: 80 KB in flight), and the chunk's segment
-// minima are staged for SPC_STAGE segments at a time (flushed to segmin as soon as they
-// close) to leave the LDS for the ring.
+// (11.6 B per cycle and CU at full rate), so stages land in a ring of RING buffers, RING - 1
+// stages ahead (the 64-slot form: ring 2 of 16-KiB stages at 4 blocks per CU, 64 KB in flight),
+// and the chunk's segment minima are staged for SPC segments at a time (flushed to segmin as
+// soon as they close) to leave the LDS for the ring.
 
-// CMP: the compact form (RK_TILE_H8 per tile, one MFMA per chain; stages of 8 KiB)
-template <int G, int W, bool CMP = false>
+// wait until at most `ahead` (<= MAXA) of this wave's stages (NP loads each) are in flight
+template <int NP, int MAXA>
+__device__ __forceinline__ void wait_stages(int ahead) {
+    if constexpr (MAXA == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+        static_assert(NP * MAXA < 64, "vmcnt is a 6-bit count");
+        if (ahead >= MAXA) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * MAXA) : "memory");
+        else wait_stages<NP, MAXA - 1>(ahead);
+    }
+}
+
+// CMP: the compact form (RK_TILE_H8 per tile, one MFMA per chain) with its own geometry: stages
+// of TILES tiles (4 or 8: TILES / 4 stages of the stage map, each 4 consecutive tiles), RK_RING
+// buffers, RK_SPC staged segments; nstage counts stages of TILES tiles, s0 the part's first
+// stage in the stage map's units
+template <int G, int W, bool CMP = false, int TILES = STAGE_TILES>
 __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *sbuf, int *smin,
                                          const StageMap &sm, long chunk, int s0, int nstage, int tps,
                                          const half8 *__restrict__ q16, float *__restrict__ segmin,
                                          long seg0, long nseg, int q0, int M) {
     static_assert(!CMP || RK_BUILT, "the compact form needs the 16x16x32 shape at P = 3");
+    static_assert(TILES % STAGE_TILES == 0 && (CMP || TILES == STAGE_TILES), "stage geometry");
+    constexpr int RING = CMP ? RK_RING : R16_RING, SPC = CMP ? RK_SPC : SPC_STAGE;
+    constexpr int MS = TILES / STAGE_TILES;   // stage-map stages per stage
     constexpr int NS = R16_S16 ? c16_ns<G, W>() : bal_ns(G, W);
     constexpr int T0 = bal_t0(G, W);
-    // half8 per tile and stage, 1 KiB pieces each wave copies per stage
-    constexpr int TH8 = CMP ? RK_TILE_H8 : R16_TILE_H8, SH8 = STAGE_TILES * TH8, NP = SH8 / 256;
+    // half8 per tile, map stage and stage; 1 KiB pieces each wave copies per map stage and stage
+    constexpr int TH8 = CMP ? RK_TILE_H8 : R16_TILE_H8, MH8 = STAGE_TILES * TH8, SH8 = MS * MH8;
+    constexpr int NPM = MH8 / 256, NP = MS * NPM;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     half8 bq[NS][CMP ? 1 : R16_S16 ? 2 : R16_MFMA];
@@ -415,44 +457,62 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
             for (int m = 0; m < R16_MFMA; ++m) bq[k][m] = p[m];
         }
     }
-    // one stage = 4 consecutive tiles: 4 R16_MFMA wave-instructions of 1 KiB, R16_MFMA per wave
+    // one map stage = 4 consecutive tiles: 4 NPM wave-instructions of 1 KiB, NPM per wave
     auto issue = [&](int s) {
-        const half8 *src = db16 + (stage_lrow(sm, chunk, s0 + s) >> 5) * TH8 + W * 64 + lane;
-        half8 *dst = sbuf + (s % R16_RING) * SH8 + W * 64;
+        if constexpr (MS == 1) {
+            const half8 *src = db16 + (stage_lrow(sm, chunk, s0 + s) >> 5) * TH8 + W * 64 + lane;
+            half8 *dst = sbuf + (s % RING) * SH8 + W * 64;
 #pragma unroll
-        for (int k = 0; k < NP; ++k)
-            __builtin_amdgcn_global_load_lds((const void *)(src + k * 256), (void *)(dst + k * 256), 16, 0, 2);
+            for (int k = 0; k < NP; ++k)
+                __builtin_amdgcn_global_load_lds((const void *)(src + k * 256), (void *)(dst + k * 256), 16, 0, 2);
+        } else {
+#pragma unroll
+            for (int h = 0; h < MS; ++h) {
+                const half8 *src = db16 + (stage_lrow(sm, chunk, s0 + s * MS + h) >> 5) * TH8 + W * 64 + lane;
+                half8 *dst = sbuf + (s % RING) * SH8 + h * MH8 + W * 64;
+#pragma unroll
+                for (int k = 0; k < NPM; ++k)
+                    __builtin_amdgcn_global_load_lds((const void *)(src + k * 256), (void *)(dst + k * 256), 16, 0,
+                                                     2);
+            }
+        }
     };
     float mn[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) mn[k] = FLT_MAX;
-    const int spc = nstage * STAGE_TILES / tps;
+    const int spc = nstage * TILES / tps;
 #pragma unroll
-    for (int s = 0; s < R16_RING - 1; ++s)
+    for (int s = 0; s < RING - 1; ++s)
         if (s < nstage) issue(s);
-    // stage 0 landed (the later stages' loads may stay in flight)
-    if (nstage > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (R16_RING - 2)) : "memory");
+    // stage 0 landed (the later stages issued, RING - 2 or all the part has, may stay in flight;
+    // the 64-slot form keeps its instructions: it drains the ring at a part's end)
+    if constexpr (CMP) wait_stages<NP, RING - 2>(nstage - 1);
+    else if (nstage > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (RING - 2)) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     stage_barrier();
     for (int s = 0; s < nstage; ++s) {
-        const bool more = s + R16_RING - 1 < nstage;
-        if (more) issue(s + R16_RING - 1);   // into the buffer stage s - 1 used (consumed)
+        const bool more = s + RING - 1 < nstage;
+        if (more) issue(s + RING - 1);   // into the buffer stage s - 1 used (consumed)
         if constexpr (CMP) {
-            r16_stage_s16k<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
-            r16_close_s16<G, W, NS>(s, tps, smin, mn, lane);
+            // (one copy of the stage body: unrolled, the two bodies of an 8-tile stage keep both
+            // sets of operands live at G = 5, 7 and 9 and spill)
+#pragma nounroll
+            for (int h = 0; h < MS; ++h)
+                r16_stage_s16k<G, W, NS>(sbuf + (s % RING) * SH8 + h * MH8, bq, mn, lane);
+            r16_close_s16<G, W, NS, TILES, SPC>(s, tps, smin, mn, lane);
         } else if constexpr (R16_S16) {
-            r16_stage_s16<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
+            r16_stage_s16<G, W, NS>(sbuf + (s % RING) * SH8, bq, mn, lane);
             r16_close_s16<G, W, NS>(s, tps, smin, mn, lane);
         } else {
-            r16_stage<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
+            r16_stage<G, W, NS>(sbuf + (s % RING) * SH8, bq, mn, lane);
             r16_close<G, W, NS>(s, tps, smin, mn, lane);
         }
-        const int done = (s + 1) * STAGE_TILES;
+        const int done = (s + 1) * TILES;
         if (done % tps == 0) {
             const int sg = done / tps - 1;            // the segment this stage closed
-            if (sg % SPC_STAGE == SPC_STAGE - 1 || sg == spc - 1) {
+            if (sg % SPC == SPC - 1 || sg == spc - 1) {
                 stage_barrier();                      // every wave's minima of these segments
-                const int base = sg - sg % SPC_STAGE, n = sg - base + 1;
+                const int base = sg - sg % SPC, n = sg - base + 1;
                 for (int i = tid; i < G * 32 * n; i += 256) {
                     const int ql = i / n, k = i - ql * n;
                     int *e = &smin[k * (G * 32) + ql];
@@ -465,8 +525,10 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
                 }
             }
         }
-        // stage s + 1 landed: the R16_RING - 2 stages issued after it may stay in flight
-        if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (R16_RING - 2)) : "memory");
+        // stage s + 1 landed: the stages issued after it (RING - 2, fewer at the part's end) may
+        // stay in flight
+        if constexpr (CMP) wait_stages<NP, RING - 2>(nstage - 2 - s);
+        else if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (RING - 2)) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         stage_barrier();   // (every wave's reads of stage s done: its buffer is refilled next)
     }
@@ -673,14 +735,15 @@ __global__ __launch_bounds__(256, IA_R16_OCC) void k_screen16rs(const XJob *__re
 }
 
 // the compact screen (ia_rot16.h RK_*; one job): k_screen16r's grid, parts and minima over the
-// compact DB (ia_db_build_rotk) and the compact operands of the same query rows
-template <int G>
-__global__ __launch_bounds__(256, IA_R16_OCC) void k_screen16c(const half8 *__restrict__ dbk, int nchunks, int ch,
-                                                      int seg_rows, StageMap sm,
-                                                      const half8 *__restrict__ q16, int M, int groups,
-                                                      float *__restrict__ segmin, long nseg, int split) {
-    __shared__ half8 sbuf[R16_RING * STAGE_TILES * RK_TILE_H8];
-    __shared__ int smin[SPC_STAGE * G * 32];
+// compact DB (ia_db_build_rotk) and the compact operands of the same query rows, in stages of
+// TILES tiles (r16_body); nstage: the part's stages
+template <int G, int TILES>
+__global__ __launch_bounds__(256, IA_RK_OCC) void k_screen16c(const half8 *__restrict__ dbk, int nchunks, int ch,
+                                                     int seg_rows, StageMap sm,
+                                                     const half8 *__restrict__ q16, int M, int groups,
+                                                     float *__restrict__ segmin, long nseg, int split) {
+    __shared__ half8 sbuf[RK_RING * TILES * RK_TILE_H8];
+    __shared__ int smin[RK_SPC * G * 32];
     const int b = blockIdx.x;
     const int slot = b >> 3;
     const int part = (slot / groups) * 8 + (b & 7);
@@ -689,19 +752,19 @@ __global__ __launch_bounds__(256, IA_R16_OCC) void k_screen16c(const half8 *__re
     const int lsp = __builtin_ctz((unsigned)split);
     const int chunk = part >> lsp, half = part & (split - 1);
     const int spc = ch / seg_rows;
-    for (int i = threadIdx.x; i < SPC_STAGE * G * 32; i += 256) smin[i] = 0x7fffffff;
-    const int nstage = (ch / (STAGE_TILES * 32)) >> lsp;
+    for (int i = threadIdx.x; i < RK_SPC * G * 32; i += 256) smin[i] = 0x7fffffff;
+    const int nstage = (ch / (TILES * 32)) >> lsp;
     const int tps = seg_rows >> 5;
     const half8 *qg = q16 + (long)group * G * 32 * Q16_ROW;
     const long seg0 = (long)chunk * spc + (long)half * (spc >> lsp);
     const int q0 = group * G * 32;
-    const int s0 = half * nstage;
+    const int s0 = half * nstage * (TILES / STAGE_TILES);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if constexpr (RK_BUILT) {
-        if (wv == 0) r16_body<G, 0, true>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
-        else if (wv == 1) r16_body<G, 1, true>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
-        else if (wv == 2) r16_body<G, 2, true>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
-        else r16_body<G, 3, true>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+        if (wv == 0) r16_body<G, 0, true, TILES>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+        else if (wv == 1) r16_body<G, 1, true, TILES>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+        else if (wv == 2) r16_body<G, 2, true, TILES>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+        else r16_body<G, 3, true, TILES>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
     }
 }
 
@@ -1119,6 +1182,10 @@ int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Flo
            "launch_screen16r: bad chunking");
     IA_ARG(sm.sc == ch / 128, "launch_screen16r: stage map of another chunking");
     IA_ARG(njobs >= 1 && njobs <= IA_BATCH_MAX && (njobs == 1 || jobs), "launch_screen16r: bad batch");
+    // the compact form's stage: RK_TILES tiles where the segments (hence the chunks and the parts
+    // below, whole numbers of segments) are whole numbers of them, else 4 (checked above)
+    const bool wide = compact && RK_TILES != STAGE_TILES && seg_rows % (RK_TILES * 32) == 0;
+    const int occ = compact ? IA_RK_OCC : IA_R16_OCC;
     const half8 *db16 = reinterpret_cast<const half8 *>(dbr);
     const half8 *q = reinterpret_cast<const half8 *>(q16);
     const int T = (M + 31) / 32;
@@ -1134,7 +1201,7 @@ int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Flo
     }();
     const int spc = ch / seg_rows;
     int split = 1;
-    while (2 * split <= spc && nchunks * 2 * split * groups * njobs <= cus * IA_R16_OCC) split *= 2;
+    while (2 * split <= spc && nchunks * 2 * split * groups * njobs <= cus * occ) split *= 2;
     const long nb = ((nchunks * split + 7) / 8) * 8 * groups;
     IA_ARG(nb < (1L << 31), "screen grid too large");
     const dim3 grid((unsigned)nb, (unsigned)njobs);
@@ -1149,9 +1216,13 @@ int launch_screen16r(const void *dbr, long nrows, const StageMap &sm, const _Flo
     const dim3 gridw((unsigned)(((nsb + 7) / 8) * 8 * groups), (unsigned)njobs);
 #define IA_R16_CASE(GG)                                                                             \
     case GG:                                                                                        \
-        if (compact)                                                                                \
-            k_screen16c<GG><<<grid, 256, 0, st>>>(db16, (int)nchunks, ch, seg_rows, sm, q, M,       \
-                                                  groups, segmin, nseg, split);                     \
+        if (wide)                                                                                   \
+            k_screen16c<GG, RK_TILES><<<grid, 256, 0, st>>>(db16, (int)nchunks, ch, seg_rows, sm,   \
+                                                            q, M, groups, segmin, nseg, split);     \
+        else if (compact)                                                                           \
+            k_screen16c<GG, STAGE_TILES><<<grid, 256, 0, st>>>(db16, (int)nchunks, ch, seg_rows,    \
+                                                               sm, q, M, groups, segmin, nseg,      \
+                                                               split);                              \
         else if (wform)                                                                             \
             k_screen16w<GG><<<gridw, 512, 0, st>>>(db16, (int)nsb, spb, tps, seg_rows, sm, q, M,    \
                                                    groups, segmin, nseg, jobs, parity);             \

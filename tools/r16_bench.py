@@ -3,8 +3,11 @@ dominant kernel over the 4,194,304-row rotated DB at M queries from
 tests/golden/c4_queries.npz, HIP events around reps launches (IA_LIB_PATH selects a variant
 build, tools/build_variant.sh).  Prints per M: mean us per launch, algorithmic frac of the
 f16 peak (110 flop per pair), pipe frac (160 f16 flop issued per pair), DB GB/s.
+--compact times the compact screen instead (k_screen16c over the compact DB,
+ia_diag_screen16k; DB GB/s of its 64-B rows).  'minima' is a checksum of the segment minima's
+bit patterns: builds whose minima agree bit for bit print the same value.
 
-  python tools/r16_bench.py [--M 342,256,128] [--reps 20]
+  python tools/r16_bench.py [--compact] [--M 342,256,128] [--reps 20] [--sleep CYCLES]
 """
 import argparse
 import ctypes
@@ -32,8 +35,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--M', default='342,256,128')
     ap.add_argument('--reps', type=int, default=20)
-    ap.add_argument('--sleep', type=int, default=0, help='GPU cycles of idle spin after each launch '
-                    '(torch.cuda._sleep: the product\'s gaps between screens); not counted')
+    ap.add_argument('--sleep', default='0', help='GPU cycles of idle spin after each launch '
+                    '(torch.cuda._sleep: the product\'s gaps between screens); not counted.  A comma '
+                    'list times every M once per value')
+    ap.add_argument('--compact', action='store_true', help='the compact screen (ia_diag_screen16k)')
     args = ap.parse_args()
     Ms = [int(x) for x in args.M.split(',')]
     dev = torch.device('cuda', 0)
@@ -42,8 +47,9 @@ def main():
     Ap_pyr = ip.gaussian_pyramid_dev(job.Ap, cfg.n_sm, job.levels)
     level = job.max_levels - 1
     idx = algorithms.level_index(A_pyr, [Ap_pyr], level, rot=True)
-    assert idx.dbr is not None
+    assert idx.dbr is not None and (idx.dbk is not None or not args.compact)
     lib = _ia.lib()
+    screen, db = (lib.ia_diag_screen16k, idx.dbk) if args.compact else (lib.ia_diag_screen16r, idx.dbr)
     N = idx.nrows
     g = np.load(os.path.join(ROOT, 'tests', 'golden', 'c4_queries.npz'))
     Mmax = max(Ms)
@@ -59,37 +65,41 @@ def main():
     out = []
     for M in Ms:
         def run():
-            _ia.check(lib.ia_diag_screen16r(ctypes.byref(idx.src), idx.row0, N, _ia.ptr(idx.dbr), _ia.ptr(idx.rot),
-                                            _ia.ptr(idx.amax), _ia.ptr(idx.center), _ia.ptr(q64), M, _ia.ptr(q16),
-                                            _ia.ptr(nq), _ia.ptr(nsk), _ia.ptr(segmin), st), 'screen16r')
+            _ia.check(screen(ctypes.byref(idx.src), idx.row0, N, _ia.ptr(db), _ia.ptr(idx.rot),
+                             _ia.ptr(idx.amax), _ia.ptr(idx.center), _ia.ptr(q64), M, _ia.ptr(q16),
+                             _ia.ptr(nq), _ia.ptr(nsk), _ia.ptr(segmin), st), 'screen16')
         for _ in range(3):
             run()
         torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if args.sleep:
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                  for _ in range(args.reps)]
-            for a, b in ev:
-                a.record()
-                run()
-                b.record()
-                torch.cuda._sleep(args.sleep)
-            torch.cuda.synchronize()
-            us = sum(a.elapsed_time(b) for a, b in ev) * 1e3 / args.reps
-        else:
-            e0.record()
-            for _ in range(args.reps):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
-            us = e0.elapsed_time(e1) * 1e3 / args.reps
-        pairs = M * N
-        out.append({'M': M, 'us': round(us, 1), 'frac': 110 * pairs / (us * 1e-6) / 1e12 / F16_PEAK,
-                    'pipe_frac': 2 * lib.ia_db_rot_slots() * pairs / (us * 1e-6) / 1e12 / F16_PEAK,
-                    'P': lib.ia_db_rot_components(),
-                    'db_gbs': lib.ia_db_rot_bytes(N) / (us * 1e-6) / 1e9,
-                    'sleep': args.sleep, 'lib': os.environ.get('IA_LIB_PATH', 'libia.so')})
-        print(json.dumps(out[-1]), flush=True)
+        for sleep in [int(x) for x in args.sleep.split(',')]:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            if sleep:
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                      for _ in range(args.reps)]
+                for a, b in ev:
+                    a.record()
+                    run()
+                    b.record()
+                    torch.cuda._sleep(sleep)
+                torch.cuda.synchronize()
+                us = sum(a.elapsed_time(b) for a, b in ev) * 1e3 / args.reps
+            else:
+                e0.record()
+                for _ in range(args.reps):
+                    run()
+                e1.record()
+                torch.cuda.synchronize()
+                us = e0.elapsed_time(e1) * 1e3 / args.reps
+            pairs = M * N
+            db_bytes = lib.ia_db_rotk_bytes(N) if args.compact else lib.ia_db_rot_bytes(N)
+            minima = int(segmin[:M].view(torch.int32).to(torch.int64).sum().item())
+            slots = 32 if args.compact else lib.ia_db_rot_slots()
+            out.append({'M': M, 'us': round(us, 1), 'frac': 110 * pairs / (us * 1e-6) / 1e12 / F16_PEAK,
+                        'pipe_frac': 2 * slots * pairs / (us * 1e-6) / 1e12 / F16_PEAK,
+                        'P': lib.ia_db_rot_components(),
+                        'db_gbs': db_bytes / (us * 1e-6) / 1e9, 'compact': args.compact,
+                        'minima': minima, 'sleep': sleep, 'lib': os.environ.get('IA_LIB_PATH', 'libia.so')})
+            print(json.dumps(out[-1]), flush=True)
 
 
 if __name__ == '__main__':
