@@ -31,7 +31,7 @@ _dp = ctypes.c_void_p
 class IaSrcLevel(ctypes.Structure):
     _fields_ = [('A_sm', _dp), ('A_lg', _dp), ('Ap_sm', _dp), ('Ap_lg', _dp),
                 ('A_hs', ctypes.c_int), ('A_ws', ctypes.c_int), ('Ah', ctypes.c_int),
-                ('Aw', ctypes.c_int), ('nAp', ctypes.c_int)]
+                ('Aw', ctypes.c_int), ('nAp', ctypes.c_int), ('nA', ctypes.c_int)]
 
 
 class IaLsh(ctypes.Structure):
@@ -445,14 +445,24 @@ def workspace(nbytes):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
 
 
-def src_level(A_sm, A_lg, Ap_sm, Ap_lg):
-    """IaSrcLevel over device tensors (Ap_*: stacked (nAp, h, w))."""
+def src_level(A_sm, A_lg, Ap_sm, Ap_lg, nA=1):
+    """IaSrcLevel over device tensors (Ap_*: stacked (nAp, h, w)).  nA = 1: A_* are one A
+    image (h, w); nA = nAp > 1: training pairs, A_* stacked (nA, h, w) like Ap_*.  nA is the
+    caller's statement, never read off the tensors' rank (a luminance stack and a colour image
+    have the same rank)."""
+    nA = int(nA)
+    if nA not in (1, int(Ap_lg.shape[0])):
+        raise ValueError('nA must be 1 (one A) or the number of A\' images (training pairs), not %d' % nA)
+    for t, what in ((A_sm, 'A_sm'), (A_lg, 'A_lg')):
+        if nA > 1 and tuple(t.shape) != (nA,) + tuple(t.shape[-2:]):
+            raise ValueError('%s: shape %s does not hold %d stacked luminance images' % (what, tuple(t.shape), nA))
     s = IaSrcLevel()
     s.A_sm, s.A_lg, s.Ap_sm, s.Ap_lg = (ptr(A_sm).value, ptr(A_lg).value, ptr(Ap_sm).value,
                                         ptr(Ap_lg).value)
     s.A_hs, s.A_ws = A_sm.shape[-2:]
     s.Ah, s.Aw = A_lg.shape[-2:]
     s.nAp = Ap_lg.shape[0]
+    s.nA = nA
     return s
 
 

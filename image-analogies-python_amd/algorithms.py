@@ -83,6 +83,24 @@ def lsh_params(c):
                 width=getattr(c, 'lsh_width', 1.0), seed=getattr(c, 'lsh_seed', 0))
 
 
+def a_pyramids(A_pyr):
+    """The A pyramids of a run as a list: A_pyr is one pyramid (a list of level tensors) or,
+    for training pairs (A_i, A'_i), a list of n pyramids (A_pyr[0] is itself a list)."""
+    return list(A_pyr) if isinstance(A_pyr[0], (list, tuple)) else [A_pyr]
+
+
+def a_level(A_pyr, nAp, level):
+    """(A_sm, A_lg, nA) of one level: the one A's tensors and nA = 1, or for n = nAp training
+    pairs the n A images stacked like the A' images and nA = n.  A 1-element list of pyramids
+    is the single A; any other count raises ValueError."""
+    pyrs = a_pyramids(A_pyr)
+    if len(pyrs) == 1:
+        return pyrs[0][level - 1], pyrs[0][level], 1
+    if len(pyrs) != nAp:
+        raise ValueError('%d A pyramids for %d A\' pyramids: training pairs need one A per A\'' % (len(pyrs), nAp))
+    return torch.stack([p[level - 1] for p in pyrs]), torch.stack([p[level] for p in pyrs]), len(pyrs)
+
+
 class LevelIndex:
     """Device-resident As[level] for rows [row0, row0 + nrows) (a shard when sharded).
 
@@ -91,12 +109,17 @@ class LevelIndex:
     split pair per pixel) where the level allows it, else the 224-B rows of ia_db_build.  Centre = the means
     of A (34 A dims) and of the A' images (21 A' dims): any centre is exact for the
     distances; centring only tightens the screen's error bound.
+
+    nA = nAp > 1: training pairs, A_sm / A_lg stacked (nA, h, w) like the A' images and row
+    (i, r, c) = [full(A_i) | half(A'_i)]; the centre and the LSH width then take their statistics
+    over all A images, and the level runs from the 224-B rows (no image form for pairs).
     """
 
-    def __init__(self, A_sm, A_lg, Ap_sm, Ap_lg, row0=0, nrows=None, rows=None, rot=False):
+    def __init__(self, A_sm, A_lg, Ap_sm, Ap_lg, row0=0, nrows=None, rows=None, rot=False, nA=1):
         self.A_sm, self.A_lg = A_sm.contiguous(), A_lg.contiguous()
         self.Ap_sm, self.Ap_lg = Ap_sm.contiguous(), Ap_lg.contiguous()
-        self.src = _ia.src_level(self.A_sm, self.A_lg, self.Ap_sm, self.Ap_lg)
+        self.nA = int(nA)
+        self.src = _ia.src_level(self.A_sm, self.A_lg, self.Ap_sm, self.Ap_lg, self.nA)
         self.N = int(Ap_lg.shape[0] * Ap_lg.shape[1] * Ap_lg.shape[2])
         self.row0 = int(row0)
         self.nrows = self.N - self.row0 if nrows is None else int(nrows)
@@ -225,8 +248,11 @@ class LevelIndex:
 
     def features(self):
         """The full fp64 As[level] matrix (N x 55), materialised on demand."""
-        A = level_features_dev(self.A_sm, self.A_lg, True)
-        rows = [torch.cat([A, level_features_dev(self.Ap_sm[i], self.Ap_lg[i], False)], 1)
+        if self.nA > 1:
+            A = [level_features_dev(self.A_sm[i], self.A_lg[i], True) for i in range(self.nA)]
+        else:
+            A = [level_features_dev(self.A_sm, self.A_lg, True)] * self.Ap_lg.shape[0]
+        rows = [torch.cat([A[i], level_features_dev(self.Ap_sm[i], self.Ap_lg[i], False)], 1)
                 for i in range(self.Ap_lg.shape[0])]
         return torch.cat(rows, 0)
 
@@ -331,7 +357,8 @@ def rot3_build(db3, N):
 
 def lsh3_tables(A_lg, Ap_lg, db3, N, tables=16, hashes=4, width=1.0, seed=0):
     """The LSH tables of a 3-channel level's N materialised rows (db3: its ia_db3_build
-    buffer; A_lg (h, w, 3) and Ap_lg (nAp, h, w, 3): the level's fine images).  The centre is
+    buffer; A_lg (h, w, 3), or (nA, h, w, 3) for training pairs (the statistics are over all of
+    them), and Ap_lg (nAp, h, w, 3): the level's fine images).  The centre is
     mean(A_lg) for the 102 A dims and mean(Ap_lg) for the 63 A' dims, the bucket width
     ``width`` x max(sqrt((102 var(A_lg) + 63 var(Ap_lg)) / 165), 1e-6), the projections
     lsh_projections(..., dim=165).  Returns (IaLsh, centre (165, device), the projections on
@@ -364,15 +391,21 @@ class LevelIndex3:
     (ia_match3_batch) — exact like LevelIndex; build_lsh() switches it to the approximate
     LSH matcher (ia_lsh3_build / ia_lsh3_match_batch)."""
 
-    def __init__(self, A_sm, A_lg, Ap_sm, Ap_lg):
+    def __init__(self, A_sm, A_lg, Ap_sm, Ap_lg, nA=1):
+        """nA = nAp > 1: training pairs, A_sm / A_lg stacked (nA, h, w, 3) like the A' images."""
         self.A_sm, self.A_lg = A_sm.contiguous(), A_lg.contiguous()
         self.Ap_sm, self.Ap_lg = Ap_sm.contiguous(), Ap_lg.contiguous()
+        self.nA = int(nA)
+        if self.nA not in (1, int(self.Ap_lg.shape[0])) or (
+                self.nA > 1 and tuple(self.A_lg.shape) != tuple(self.Ap_lg.shape)):
+            raise ValueError('nA must be 1 (one A) or the number of A\' images (A stacked like A\')')
         src = _ia.IaSrcLevel()
         src.A_sm, src.A_lg, src.Ap_sm, src.Ap_lg = (_ia.ptr(self.A_sm).value, _ia.ptr(self.A_lg).value,
                                                     _ia.ptr(self.Ap_sm).value, _ia.ptr(self.Ap_lg).value)
-        src.A_hs, src.A_ws = self.A_sm.shape[:2]
-        src.Ah, src.Aw = self.A_lg.shape[:2]
+        src.A_hs, src.A_ws = self.Ap_sm.shape[1:3]
+        src.Ah, src.Aw = self.Ap_lg.shape[1:3]
         src.nAp = self.Ap_lg.shape[0]
+        src.nA = self.nA
         self.src = src
         self.N = int(src.nAp * src.Ah * src.Aw)
         self.shape = (self.N, 165)
@@ -446,7 +479,8 @@ class _LazyAs(list):
 
 
 def level_index(A_pyr, Ap_pyr_list, level, row_range=None, lsh=None, rows=None, rot=None):
-    """Device index of one level from device pyramids.  row_range(level, N) ->
+    """Device index of one level from device pyramids (A_pyr: one pyramid, or one per A'
+    pyramid for training pairs: a_pyramids).  row_range(level, N) ->
     (row0, nrows) selects this rank's shard of the rows; lsh (dict of build_lsh
     arguments) switches it to the LSH matcher; rows=True keeps the row form next to the
     image form; rot (default: the exact matcher on a level or shard of at least
@@ -457,30 +491,36 @@ def level_index(A_pyr, Ap_pyr_list, level, row_range=None, lsh=None, rows=None, 
     r0, nr = (0, N) if row_range is None else row_range(level, N)
     if rot is None:
         rot = lsh is None and _ia.db_rot_enabled() and nr >= _ia.rot_min_rows()
-    index = LevelIndex(A_pyr[level - 1], A_pyr[level], Ap_sm, Ap_lg, r0, nr, rows=rows, rot=rot)
+    A_sm, A_lg, nA = a_level(A_pyr, len(Ap_pyr_list), level)
+    index = LevelIndex(A_sm, A_lg, Ap_sm, Ap_lg, r0, nr, rows=rows, rot=rot, nA=nA)
     if lsh is not None:
         index.build_lsh(**lsh)
     return index
 
 
 def create_index_dev(A_pyr, Ap_pyr_list, max_levels, row_range=None, lsh=None):
-    """Device index per level 1..max_levels-1 (entry 0 unused)."""
+    """Device index per level 1..max_levels-1 (entry 0 unused); A_pyr as level_index takes it."""
     return [None] + [level_index(A_pyr, Ap_pyr_list, l, row_range, lsh)
                      for l in range(1, max_levels)]
 
 
 def create_index(A_pyr, Ap_pyr_list, c):
-    """Per-level database of [A full | A'_i half] rows (algorithms.py:50-70).  Returns
+    """Per-level database of [A full | A'_i half] rows (algorithms.py:50-70); with A_pyr a list of
+    len(Ap_pyr_list) pyramids, of the training pairs' rows [A_i full | A'_i half].  Returns
     (index, params, As, As_size) in the reference's shape: ``index[level]`` replaces the
     FLANN object, ``params[level]`` describes it, ``As`` materialises lazily."""
     dev = _ia.require_device()
-    A_dev = [_ia.to_dev(p) for p in A_pyr]
+    if len(a_pyramids(A_pyr)) not in (1, len(Ap_pyr_list)):
+        raise ValueError('%d A pyramids for %d A\' pyramids: training pairs need one A per A\''
+                         % (len(a_pyramids(A_pyr)), len(Ap_pyr_list)))
+    A_dev = [[_ia.to_dev(p) for p in pyr] for pyr in a_pyramids(A_pyr)]
     Ap_dev = [[_ia.to_dev(p) for p in pyr] for pyr in Ap_pyr_list]
     lsh = lsh_params(c)
-    if A_dev[0].dim() == 3:      # 3 channels: materialised rows, exact search or LSH
-        index = [None] + [LevelIndex3(A_dev[l - 1], A_dev[l],
+    if A_dev[0][0].dim() == 3:      # 3 channels: materialised rows, exact search or LSH
+        index = [None] + [LevelIndex3(*a_level(A_dev, len(Ap_dev), l)[:2],
                                       torch.stack([p[l - 1] for p in Ap_dev]),
-                                      torch.stack([p[l] for p in Ap_dev]))
+                                      torch.stack([p[l] for p in Ap_dev]),
+                                      nA=a_level(A_dev, len(Ap_dev), l)[2])
                           for l in range(1, c.max_levels)]
         if lsh is not None:
             for ix in index[1:]:

@@ -14,6 +14,11 @@ longer accepts as indices).  Fields added by this build (SURV
              the rows' RMS per-dimension spread) and projection seed lsh_seed;
              for luminance and for 3-channel matching (convert=False on colour images)
              alike, on one GPU (sharded levels run the exact matcher)
+
+Training pairs need no field: ``image_analogies_main(A_fname, Ap_fname_list, ...)`` takes a
+list of ``len(Ap_fname_list)`` A files and pairs A_i with A'_i (a database row is then
+[full(A_i) | half(A'_i)]); ``remap_lum`` then remaps each pair with its own A's statistics
+and ``AB_weight`` scales every A.
 """
 import numpy as np
 

@@ -100,10 +100,11 @@ __device__ __forceinline__ double feat3(const Img3 &sm, const Img3 &lg, int r, i
     return lg.at(r + t / 5 - 2, c + t % 5 - 2, ch);
 }
 
-// one thread per (row, feature): the materialised database rows [A full | A'_img half]
-__global__ __launch_bounds__(256) void k_db3_build(Img3 Asm, Img3 Alg, const double *Ap_sm,
-                                                   const double *Ap_lg, long row0, long nrows,
-                                                   double *__restrict__ db3) {
+// one thread per (row, feature): the materialised database rows [A full | A'_img half]; the A
+// of image img lies a_sm / a_lg doubles per image after Asm / Alg (0: one A for every A' image)
+__global__ __launch_bounds__(256) void k_db3_build(Img3 Asm, Img3 Alg, long a_sm, long a_lg,
+                                                   const double *Ap_sm, const double *Ap_lg, long row0,
+                                                   long nrows, double *__restrict__ db3) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= nrows * D3P) return;
     const long lr = i / D3P;
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void k_db3_build(Img3 Asm, Img3 Alg, const dou
         const long rem = ix - img * hw;
         const int r = (int)(rem / Alg.w), c = (int)(rem - (long)(rem / Alg.w) * Alg.w);
         if (k < D3_FULL) {
-            v = feat3(Asm, Alg, r, c, k);
+            v = feat3(Img3{Asm.p + img * a_sm, Asm.h, Asm.w}, Img3{Alg.p + img * a_lg, Alg.h, Alg.w}, r, c, k);
         } else {
             const Img3 psm{Ap_sm + img * (long)Asm.h * Asm.w * 3, Asm.h, Asm.w};
             const Img3 plg{Ap_lg + img * hw * 3, Alg.h, Alg.w};
@@ -1308,6 +1309,7 @@ __global__ __launch_bounds__(256) void k_lsh3_pixelb(const L3Job *__restrict__ j
 struct Src3 {
     Img3 Asm, Alg;
     const double *Ap_sm, *Ap_lg;
+    int pairs;         // training pairs: A image i goes with A' image i (0: one A for every A' image)
 };
 // acc8_row for a row that is not materialised here: features k = j + 8 i of DB pixel (r, c)
 // of A' image img gathered from the pyramids, exactly the values k_db3_build writes, and the
@@ -1316,8 +1318,12 @@ struct Src3 {
 // waiting kernel's VGPRs stay small.
 __device__ __forceinline__ Acc8 acc8_feat(const Src3 &s, int img, int r, int c, int j, const double *qs,
                                           const double *ws) {
-    const double *psm = s.Ap_sm + (long)img * s.Asm.h * s.Asm.w * 3;
-    const double *plg = s.Ap_lg + (long)img * s.Alg.h * s.Alg.w * 3;
+    // (the A half of the row: image img of training pairs, stacked as the A' images are)
+    const long osm = (long)s.Asm.h * s.Asm.w * 3, olg = (long)s.Alg.h * s.Alg.w * 3;
+    const int aimg = s.pairs ? img : 0;
+    const double *psm = s.Ap_sm + img * osm, *plg = s.Ap_lg + img * olg;
+    const long asm_ = aimg * osm, alg_ = aimg * olg;   // (offsets: a select of four per-lane pointers
+                                                       // compiled to a table in scratch memory)
     // feat3's sample of the pair (A | A' of image img; one shape) with every choice a select of
     // scalars (feat3's own branches over two Img3 temporaries put them in scratch here)
     auto ld = [&](int k) __attribute__((always_inline)) {
@@ -1329,7 +1335,7 @@ __device__ __forceinline__ Acc8 acc8_feat(const Src3 &s, int img, int r, int c, 
         const int dr = co ? t / 3 - 1 : t / 5 - 2, dc = co ? t % 3 - 1 : t % 5 - 2;
         const int h = co ? s.Asm.h : s.Alg.h, w = co ? s.Asm.w : s.Alg.w;
         const double *p = co ? (ap ? psm : s.Asm.p) : (ap ? plg : s.Alg.p);
-        return p[((long)symi2((co ? r >> 1 : r) + dr, h) * w + symi2((co ? c >> 1 : c) + dc, w)) * 3 + ch];
+        return p[(ap ? 0 : (co ? asm_ : alg_)) + ((long)symi2((co ? r >> 1 : r) + dr, h) * w + symi2((co ? c >> 1 : c) + dc, w)) * 3 + ch];
     };
     constexpr int G = 5;   // gathers in flight
     double hp[2], hw[2];
@@ -1642,6 +1648,7 @@ struct Level3 {
         IA_ARG(a && a->db && a->B_sm && a->B_lg && a->Bp_sm && a->Bp_lg && a->weights && a->s && a->im &&
                    a->workspace && a->H > 0 && a->W > 0,
                "ia_synth_level3: bad args");
+        IA_SRC_NA(a->src, "ia_synth_level3");
         {
             const int rc = lsh3_level_check(*a, "ia_synth_level3");
             if (rc) return rc;
@@ -1669,7 +1676,7 @@ struct Level3 {
         W = a->W;
         ws3_layout(H, W, a->nrows, reinterpret_cast<char *>(a->workspace), &w, sharded ? nranks : 0);
         src3 = Src3{Img3{a->src.A_sm, a->src.A_hs, a->src.A_ws}, Img3{a->src.A_lg, a->src.Ah, a->src.Aw},
-                    a->src.Ap_sm, a->src.Ap_lg};
+                    a->src.Ap_sm, a->src.Ap_lg, src_pairs(a->src) ? 1 : 0};
         nb = match3_blocks(a->nrows);
         Bsm = Img3{a->B_sm, a->B_hs, a->B_ws};
         Blg = Img3{a->B_lg, H, W};
@@ -1914,12 +1921,15 @@ size_t ia_db3_bytes(long nrows) {
 
 int ia_db3_build(const IaSrcLevel *src, long row0, long nrows, double *db3, void *stream) {
     IA_ARG(src && db3 && nrows > 0 && row0 >= 0, "ia_db3_build: bad args");
+    IA_SRC_NA(*src, "ia_db3_build");
     IA_ARG(row0 + nrows <= (long)src->nAp * src->Ah * src->Aw, "ia_db3_build: rows out of range");
     const Img3 Asm{src->A_sm, src->A_hs, src->A_ws}, Alg{src->A_lg, src->Ah, src->Aw};
     const long n = nrows * D3P;
     hipStream_t st = S(stream);
-    k_db3_build<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(Asm, Alg, src->Ap_sm, src->Ap_lg,
-                                                            row0, nrows, db3);
+    const bool pairs = src_pairs(*src);
+    k_db3_build<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
+        Asm, Alg, pairs ? (long)src->A_hs * src->A_ws * 3 : 0, pairs ? (long)src->Ah * src->Aw * 3 : 0,
+        src->Ap_sm, src->Ap_lg, row0, nrows, db3);
     // the split-f16 rows of the screen: range -> centre and bound -> split
     const Db3View v = db3_view(db3, nrows);
     IA_HIP(hipMemsetAsync(v.meta->rng, 0xff, sizeof(v.meta->rng), st));
@@ -2005,6 +2015,7 @@ size_t ia_synth3_shard_workspace_bytes(int H, int W, long nrows, int nranks) {
 
 int ia_level3_resources(const IaSynthArgs *a, int *out) {
     IA_ARG(a && out && a->nrows > 0, "ia_level3_resources: bad args");
+    IA_SRC_NA(a->src, "ia_level3_resources");
     const bool rot = g_color16.load(std::memory_order_relaxed) != 0 && a->dbr && a->rot;
     hipFuncAttributes f{}, sc{};
     IA_HIP(hipFuncGetAttributes(&f, reinterpret_cast<const void *>(&k_peer_finish3)));
@@ -2118,7 +2129,7 @@ static int synth_levels3(const IaSynthArgs *levels, int n, int K, void *stream) 
                 const IaSynthArgs &b = levels[(size_t)j * K + k];
 #define IA_SAME(field) IA_ARG(b.field == a.field, who + ": the jobs of a batch differ in " #field)
                 IA_SAME(H); IA_SAME(W); IA_SAME(B_hs); IA_SAME(B_ws);
-                IA_SAME(src.Ah); IA_SAME(src.Aw); IA_SAME(src.A_hs); IA_SAME(src.A_ws); IA_SAME(src.nAp);
+                IA_SAME(src.Ah); IA_SAME(src.Aw); IA_SAME(src.A_hs); IA_SAME(src.A_ws); IA_SAME(src.nAp); IA_SAME(src.nA);
                 IA_SAME(nrows);
 #undef IA_SAME
                 // jobs passing one rotated DB are one DB group (ia_batch3_groups): it stands for
@@ -2128,7 +2139,7 @@ static int synth_levels3(const IaSynthArgs *levels, int n, int K, void *stream) 
                     if (c.dbr != b.dbr) continue;
 #define IA_SAME(field) IA_ARG(b.field == c.field, who + ": jobs sharing a dbr differ in " #field)
                     IA_SAME(db); IA_SAME(rot); IA_SAME(nrows);
-                    IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg);
+                    IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg); IA_SAME(src.nA);
 #undef IA_SAME
                     break;   // (p agrees with the group's earlier jobs already)
                 }
@@ -2212,7 +2223,7 @@ int ia_synth_levels3_lsh_batch(const IaSynthArgs *levels, int n, int K, void *st
             }
 #define IA_SAME(field) IA_ARG(b.field == a.field, who + ": the jobs of an lsh batch differ in " #field)
             IA_SAME(H); IA_SAME(W); IA_SAME(B_hs); IA_SAME(B_ws);
-            IA_SAME(src.Ah); IA_SAME(src.Aw); IA_SAME(src.A_hs); IA_SAME(src.A_ws); IA_SAME(src.nAp);
+            IA_SAME(src.Ah); IA_SAME(src.Aw); IA_SAME(src.A_hs); IA_SAME(src.A_ws); IA_SAME(src.nAp); IA_SAME(src.nA);
             IA_SAME(nrows); IA_SAME(lsh->L); IA_SAME(lsh->k);
 #undef IA_SAME
             IA_ARG(b.row0 == 0 && b.nrows == (long)b.src.nAp * b.src.Ah * b.src.Aw,
@@ -2226,7 +2237,7 @@ int ia_synth_levels3_lsh_batch(const IaSynthArgs *levels, int n, int K, void *st
                 if (c.lsh->mem != b.lsh->mem) continue;
 #define IA_SAME(field) IA_ARG(b.field == c.field, who + ": jobs sharing lsh->mem differ in " #field)
                 IA_SAME(lsh->proj); IA_SAME(lsh->w); IA_SAME(center); IA_SAME(db);
-                IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg);
+                IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg); IA_SAME(src.nA);
 #undef IA_SAME
                 break;   // (p agrees with the group's earlier jobs already)
             }
@@ -2253,6 +2264,7 @@ int ia_synth_levels3_lsh_batch(const IaSynthArgs *levels, int n, int K, void *st
 int ia_batch3_groups(const IaSynthArgs *level_jobs, int K, int *group_of_job) {
     IA_ARG(level_jobs && group_of_job, "ia_batch3_groups: bad args");
     IA_ARG(K >= 1 && K <= IA_BATCH_MAX, "ia_batch3_groups: K out of range (1 .. 128)");
+    for (int k = 0; k < K; ++k) IA_SRC_NA(level_jobs[k].src, "ia_batch3_groups");
     return batch3_groups(level_jobs, K, group_of_job);
 }
 

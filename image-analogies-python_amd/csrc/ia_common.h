@@ -133,18 +133,31 @@ __device__ __forceinline__ void emit_feature(const ImgPair &x, const ImgPair &y,
 // A/A' database row ix -> (A, A'_img) pair and pixel (algorithms.py:63-67,
 // img_preprocess.py:96-101 Ap_ix2px).
 struct DbSrc {
-    ImgPair A, Ap;        // Ap.sm/.lg point at image 0; image i is offset i * size
+    ImgPair A, Ap;        // A.sm/.lg, Ap.sm/.lg point at image 0; image i is offset i * size
     long hw, hws;
-    __device__ __forceinline__ void locate(long ix, ImgPair &ap, int &r, int &c) const {
+    int pairs;            // training pairs (A_i, A'_i): the A images are stacked like the A' images;
+                          // 0: one A shared by every A' image (IaSrcLevel.nA)
+    // the A image that goes with A' image img
+    __host__ __device__ __forceinline__ long a_img(long img) const { return pairs ? img : 0; }
+    __device__ __forceinline__ void locate(long ix, ImgPair &a, ImgPair &ap, int &r, int &c) const {
         const long img = ix / hw;
         const long rem = ix - img * hw;
         r = (int)(rem / A.w);
         c = (int)(rem - (long)r * A.w);
+        a = A;
+        a.sm = A.sm + a_img(img) * hws;
+        a.lg = A.lg + a_img(img) * hw;
         ap = Ap;
         ap.sm = Ap.sm + img * hws;
         ap.lg = Ap.lg + img * hw;
     }
 };
+
+// IaSrcLevel.nA (ia.h): 0 or 1 one A for every A' image, nAp training pairs
+static inline bool src_nA_ok(const IaSrcLevel &s) { return s.nA == 0 || s.nA == 1 || s.nA == s.nAp; }
+static inline bool src_pairs(const IaSrcLevel &s) { return s.nA > 1; }
+#define IA_SRC_NA(s, who)                                                                  \
+    IA_ARG(::ia::src_nA_ok(s), std::string(who) + ": nA must be 0, 1 (one A) or nAp (training pairs)")
 
 static inline DbSrc make_dbsrc(const IaSrcLevel &s) {
     DbSrc d;
@@ -152,6 +165,7 @@ static inline DbSrc make_dbsrc(const IaSrcLevel &s) {
     d.Ap = ImgPair{s.Ap_sm, s.Ap_lg, s.A_hs, s.A_ws, s.Ah, s.Aw};
     d.hw = (long)s.Ah * s.Aw;
     d.hws = (long)s.A_hs * s.A_ws;
+    d.pairs = src_pairs(s) ? 1 : 0;
     return d;
 }
 
@@ -176,10 +190,10 @@ struct Pw55 {
 
 // squared distance of DB row ix to query q (55, fp64): the oracle's brute-force value.
 __device__ __forceinline__ double row_dist2(const DbSrc &src, long ix, const double *q) {
-    ImgPair ap; int r, c;
-    src.locate(ix, ap, r, c);
+    ImgPair a, ap; int r, c;
+    src.locate(ix, a, ap, r, c);
     Pw55 pw;
-    emit_feature(src.A, ap, r, c, [&](int k, double v) {
+    emit_feature(a, ap, r, c, [&](int k, double v) {
         const double x = v - q[k];
         pw.feed(k, x * x);
     });
@@ -189,10 +203,10 @@ __device__ __forceinline__ double row_dist2(const DbSrc &src, long ix, const dou
 // weighted distance (algorithms.py:133-135 restated): s = sqrt(pw(((a-q)*w)^2)); s*s
 __device__ __forceinline__ double row_wdist(const DbSrc &src, long ix, const double *q,
                                             const double *w) {
-    ImgPair ap; int r, c;
-    src.locate(ix, ap, r, c);
+    ImgPair a, ap; int r, c;
+    src.locate(ix, a, ap, r, c);
     Pw55 pw;
-    emit_feature(src.A, ap, r, c, [&](int k, double v) {
+    emit_feature(a, ap, r, c, [&](int k, double v) {
         const double x = (v - q[k]) * w[k];
         pw.feed(k, x * x);
     });

@@ -114,10 +114,10 @@ __global__ void k_level_features(ImgPair p, int full, double *out) {
 // (fp64 sum in feature order).
 __device__ __forceinline__ void db_row(const DbSrc &src, long ix, const double *__restrict__ center,
                                         float *my) {
-    ImgPair ap; int r, c;
-    src.locate(ix, ap, r, c);
+    ImgPair a, ap; int r, c;
+    src.locate(ix, a, ap, r, c);
     double n2 = 0.0;
-    emit_feature(src.A, ap, r, c, [&](int k, double v) {
+    emit_feature(a, ap, r, c, [&](int k, double v) {
         const double d = v - center[k];
         n2 += d * d;
         my[k] = (float)d;
@@ -280,6 +280,8 @@ __device__ __forceinline__ DbWinCtx db_stage(const DbSrc &src, long row0, long n
     y = __shfl(y, tid & 32);
     x0 = __shfl(x0, tid & 32);
     const double *Apl = src.Ap.lg + (long)img * src.hw, *Aps = src.Ap.sm + (long)img * src.hws;
+    // (the tile's A image: image img of training pairs, the one A otherwise)
+    const double *Al = A.lg.get() + src.a_img(img) * src.hw, *As = A.sm.get() + src.a_img(img) * src.hws;
     // every load first (one basic block: they all issue before the first LDS store), with
     // clamped columns where the lane has nothing to stage; then the stores
     const int fc0 = symi2(x0 - 2 + c, A.w);
@@ -288,14 +290,14 @@ __device__ __forceinline__ DbWinCtx db_stage(const DbSrc &src, long row0, long n
     double vf[8][2], vc[6];
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
-        const double *row = (r < 5 ? A.lg.get() : Apl) + (long)symi2(y - 2 + (r < 5 ? r : r - 5), A.h) * A.w;
+        const double *row = (r < 5 ? Al : Apl) +(long)symi2(y - 2 + (r < 5 ? r : r - 5), A.h) * A.w;
         vf[r][0] = row[fc0];
         vf[r][1] = row[fc1];
     }
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         const long ro = (long)symi2((y >> 1) - 1 + r, A.hs) * A.ws + cc;
-        vc[r] = A.sm[ro];
+        vc[r] = As[ro];
         vc[3 + r] = Aps[ro];
     }
     double *w = win + u * WIN;
@@ -921,8 +923,9 @@ int ia_diag_set_db_build_form(int tiled) {
 int ia::launch_db_amax(const IaSrcLevel *src, const DbSrc &d, const double *center, float *amax,
                        double *part, hipStream_t st) {
     DbSpans sp;   // blocks per image in proportion to its size, at least one each
-    sp.x[0] = src->A_sm; sp.n[0] = d.hws;
-    sp.x[1] = src->A_lg; sp.n[1] = d.hw;
+    const long nA = src_pairs(*src) ? src->nA : 1;   // (the bound covers every A image)
+    sp.x[0] = src->A_sm; sp.n[0] = nA * d.hws;
+    sp.x[1] = src->A_lg; sp.n[1] = nA * d.hw;
     sp.x[2] = src->Ap_sm; sp.n[2] = (long)src->nAp * d.hws;
     sp.x[3] = src->Ap_lg; sp.n[3] = (long)src->nAp * d.hw;
     const long tot = sp.n[0] + sp.n[1] + sp.n[2] + sp.n[3];
@@ -943,6 +946,7 @@ extern "C" {
 int ia_db_build(const IaSrcLevel *src, long row0, long nrows, const double *center,
                 void *db, float *amax, void *stream) {
     IA_ARG(src && center && db && amax && nrows > 0 && row0 >= 0, "ia_db_build: bad args");
+    IA_SRC_NA(*src, "ia_db_build");
     IA_ARG(row0 + nrows <= (long)src->nAp * src->Ah * src->Aw, "ia_db_build: rows out of range");
     const long npad = db_rows_padded(nrows);
     DbSrc d = make_dbsrc(*src);
@@ -962,6 +966,7 @@ int ia_db_build(const IaSrcLevel *src, long row0, long nrows, const double *cent
 
 size_t ia_db_image_bytes(const IaSrcLevel *src, long row0, long nrows) {
     if (!src || nrows <= 0 || row0 < 0) return 0;
+    if (!src_nA_ok(*src) || src_pairs(*src)) return 0;   // training pairs: the row form only
     ImgDb v;
     size_t b = 0;
     return img_db_layout(src->Ah, src->Aw, src->A_hs, src->A_ws, src->nAp, row0, nrows, nullptr, v,
@@ -971,6 +976,8 @@ size_t ia_db_image_bytes(const IaSrcLevel *src, long row0, long nrows) {
 int ia_db_build_image(const IaSrcLevel *src, long row0, long nrows, const double *center,
                       const void *db, float *amax, void *dbi, void *stream) {
     IA_ARG(src && center && amax && dbi && nrows > 0 && row0 >= 0, "ia_db_build_image: bad args");
+    IA_SRC_NA(*src, "ia_db_build_image");
+    IA_ARG(!src_pairs(*src), "ia_db_build_image: no image form for training pairs (nA > 1): build the rows");
     IA_ARG(row0 + nrows <= (long)src->nAp * src->Ah * src->Aw, "ia_db_build_image: rows out of range");
     ImgDb v;
     IA_ARG(img_db_layout(src->Ah, src->Aw, src->A_hs, src->A_ws, src->nAp, row0, nrows, dbi, v, nullptr),

@@ -252,7 +252,8 @@ struct FinishArgs {
 // outputs and control words; the screen and k_xwave take job blockIdx.y's pointers from a
 // device table of these
 struct XJob {
-    gptr<const double> A_sm, A_lg, Ap_sm, Ap_lg;   // DbSrc images
+    gptr<const double> A_sm, A_lg, Ap_sm, Ap_lg;   // DbSrc images (image 0; the A strides are the
+                                                    // launch's: the jobs of a batch agree in nA)
     gptr<const uint32_t> fa, ca, norm, ap;          // image-form DB sections (ImgDb)
     gptr<const void> db;                            // split-f16 rows
     gptr<float> segmin;
@@ -284,8 +285,9 @@ constexpr int IA_GTAB_INTS = 1 + 2 * IA_BATCH_MAX;
 // from a device table of these in the place of the XJob table.  Jobs of one DB group hold the
 // same A / A' images, tables, projections and centre; nothing writes into those.
 struct LJob {
-    gptr<const double> A_sm, A_lg, Ap_sm, Ap_lg;   // DbSrc images (Ap: image 0)
+    gptr<const double> A_sm, A_lg, Ap_sm, Ap_lg;   // DbSrc images (image 0)
     int A_hs, A_ws, Ah, Aw;
+    int pairs;                                      // training pairs: one A image per A' image
     gptr<const double> B_sm, B_lg, Bp_sm;
     gptr<double> Bp_lg;
     int B_hs, B_ws, H, W;
@@ -308,6 +310,7 @@ struct LJob {
         d.Ap = ImgPair{Ap_sm, Ap_lg, A_hs, A_ws, Ah, Aw};
         d.hw = (long)Ah * Aw;
         d.hws = (long)A_hs * A_ws;
+        d.pairs = pairs;
         return d;
     }
     // wave t's view of the level state the per-pixel tail updates
@@ -369,10 +372,14 @@ constexpr int XW_TRACE_N = 17, XW_TRACE_PX = 512, XW_TRACE_T = 4096;
 constexpr int XW_ROWS = 0, XW_IMG = 1, XW_STRIP = 2;
 bool xstrip_applies(const DbSrc &src);
 // one built instance of the fused kernel: k_xwave by form and batch (it takes the R16 bound at
-// run time, XArgs::rot) or k_xstrip (XW_STRIP) by batch, rot, cmp and split
+// run time, XArgs::rot) or k_xstrip (XW_STRIP) by batch, rot, cmp and split.  pairs: a row-form
+// level of training pairs (DbSrc::pairs): instances of their own, so that the gathers of a level
+// with one A stay the instructions they were (the offset as a run-time select cost k_xwave
+// 0.7 % at the c3 size, profiles/pairs_ab.txt)
 struct XwVariant {
     int form;
     bool batch, rot, cmp, split;
+    bool pairs = false;
 };
 const void *xwave_kernel(XwVariant v);   // null (error set): no such instance is built
 int xwave_attributes(XwVariant v, hipFuncAttributes *at);
@@ -392,9 +399,10 @@ struct LevelPlan {
     int form;          // XW_ROWS / XW_IMG / XW_STRIP, -1 without xw
     bool rk, split;    // the level has compact waves (wave_compact); two workgroups per pixel
     bool rkcol;        // rk, and the column-0 waves are compact too (wave_compact_col)
+    bool pairs;        // training pairs (IaSrcLevel.nA > 1): the row form's pair instances
     int tail;          // TailKind
     DbView v;          // (zeroed on LSH and simulated levels: their DBs are not the level's)
-    XwVariant variant(int K, bool cmp) const { return XwVariant{form, K > 1, r16, cmp, split}; }
+    XwVariant variant(int K, bool cmp) const { return XwVariant{form, K > 1, r16, cmp, split, pairs}; }
 };
 int level_plan(const IaSynthArgs &a, int K, bool sim, LevelPlan *p);
 // a strip-order level that k_xstrip serves, of at least the compact form's rows: what rk and

@@ -39,9 +39,9 @@ __global__ __launch_bounds__(256) void k_lsh_keys(DbSrc src, long row0, long nro
     if (r >= npad) return;
     float a[IA_DP];
     {
-        ImgPair ap; int rr, cc;
-        src.locate(row0 + (r < nrows ? r : nrows - 1), ap, rr, cc);
-        emit_feature(src.A, ap, rr, cc, [&](int kk, double v) { a[kk] = (float)(v - center[kk]); });
+        ImgPair ai, ap; int rr, cc;
+        src.locate(row0 + (r < nrows ? r : nrows - 1), ai, ap, rr, cc);
+        emit_feature(ai, ap, rr, cc, [&](int kk, double v) { a[kk] = (float)(v - center[kk]); });
     }
     for (int t = 0; t < L; ++t) {
         unsigned int key = 0;
@@ -291,6 +291,7 @@ int ia_lsh_build(const IaSrcLevel *src, long row0, long nrows, const double *cen
                  const IaLsh *lsh, void *stream) {
     IA_ARG(src && center && lsh && lsh->mem && lsh->proj && nrows > 0 && row0 >= 0,
            "ia_lsh_build: bad args");
+    IA_SRC_NA(*src, "ia_lsh_build");
     IA_ARG(lsh->L >= 1 && lsh->k >= 1 && lsh->L * lsh->k <= LSH_MAXH && lsh->w > 0.f,
            "ia_lsh_build: need 1 <= L*k <= 64 and w > 0");
     IA_ARG(nrows < (1L << 31), "ia_lsh_build: too many rows");

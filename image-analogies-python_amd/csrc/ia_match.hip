@@ -454,6 +454,7 @@ size_t match_scratch_bytes(int qrows, long nrows) {
 int db_view(const DbSrc &src, long row0, long nrows, const void *db, const void *dbi, DbView *v) {
     *v = DbView{};
     IA_ARG(db || dbi, "db_view: no DB (row form or image form)");
+    IA_ARG(!dbi || !src.pairs, "db_view: no image-form DB for training pairs (nA > 1)");
     IA_ARG(!dbi || img_db_layout(src.A.h, src.A.w, src.A.hs, src.A.ws, 1, row0, nrows, dbi, v->img, nullptr),
            "db_view: an image-form DB for a level it does not apply to");
     v->db = db;
@@ -628,6 +629,7 @@ int ia_match_batch(const IaMatchArgs *a, void *stream) {
     IA_HIP(hipMemsetAsync(qp, 0, (size_t)qr * IA_DP * sizeof(float), st));
     IA_HIP(hipMemsetAsync(q16, 0, (size_t)qr * Q16_ROW * sizeof(half8), st));
     IA_HIP(hipMemsetAsync(scratch, 0, WL_HEAD, st));   // empty work list
+    IA_SRC_NA(a->src, "ia_match_batch");
     const DbSrc src = make_dbsrc(a->src);
     for (int m0 = 0; m0 < a->M; m0 += MATCH_BATCH) {
         const int M = a->M - m0 < MATCH_BATCH ? a->M - m0 : MATCH_BATCH;
@@ -710,6 +712,7 @@ int ia_diag_stage_map(long row0, long nrows, int W, int Himg, int *out) {
 static int diag_screen16(const char *who, const IaSrcLevel *src, long row0, long nrows, const void *db,
                          const void *dbi, const void *q16, int M, float *segmin, void *stream) {
     IA_ARG(src && (db || dbi) && q16 && segmin && M > 0 && nrows > 0, std::string(who) + ": bad args");
+    IA_SRC_NA(*src, who);
     DbView v;
     const int rc = db_view(make_dbsrc(*src), row0, nrows, db, dbi, &v);
     if (rc) return rc;

@@ -933,9 +933,9 @@ __global__ __launch_bounds__(256) void k_db_cov(DbSrc src, long row0, long nrows
             const long i = base + threadIdx.x;
             double *x = X[threadIdx.x];
             if (i < nsamp) {
-                ImgPair ap; int r, c;
-                src.locate(row0 + i * step, ap, r, c);
-                emit_feature(src.A, ap, r, c, [&](int k, double v) { x[k] = v - center[k]; });
+                ImgPair a, ap; int r, c;
+                src.locate(row0 + i * step, a, ap, r, c);
+                emit_feature(a, ap, r, c, [&](int k, double v) { x[k] = v - center[k]; });
             } else {
                 for (int k = 0; k < IA_D; ++k) x[k] = 0.0;
             }
@@ -1016,9 +1016,9 @@ __global__ __launch_bounds__(256) void k_db_build_rot(DbSrc src, long row0, long
         const long r = row0 + (p < nrows ? p : nrows - 1);
         double d[IA_D];
         double n2 = 0.0;
-        ImgPair ap; int rr, cc;
-        src.locate(r, ap, rr, cc);
-        emit_feature(src.A, ap, rr, cc, [&](int k, double v) {
+        ImgPair ai, ap; int rr, cc;
+        src.locate(r, ai, ap, rr, cc);
+        emit_feature(ai, ap, rr, cc, [&](int k, double v) {
             d[k] = v - center[k];
             n2 += d[k] * d[k];
         });
@@ -1084,8 +1084,8 @@ __global__ __launch_bounds__(256) void k_db_build_rotk(DbSrc src, long row0, lon
     if (p < npad) {
         const long r = row0 + (p < nrows ? p : nrows - 1);
         double d[IA_D];
-        ImgPair ap; int rr, cc;
-        src.locate(r, ap, rr, cc);
+        ImgPair ai, ap; int rr, cc;   // (no compact form for training pairs: src.A is the rows' A)
+        src.locate(r, ai, ap, rr, cc);
         emit_feature(src.A, ap, rr, cc, [&](int k, double v) { d[k] = v - center[k]; });
         const Split16Db sc = split16_db_scale(amax[0]);
         half8 o[RK_SLOTS / 8];
@@ -1338,7 +1338,7 @@ extern "C" {
 int ia_db_rot_applies(const IaSrcLevel *src, long row0, long nrows) {
     // every level: the screen streams the rotated rows in the level's stage order (strips or
     // linear chunks); the fused kernel of either form takes the R16 bound
-    if (!src || nrows <= 0 || row0 < 0) return 0;
+    if (!src || nrows <= 0 || row0 < 0 || !src_nA_ok(*src)) return 0;
     return row0 + nrows <= (long)src->nAp * src->Ah * src->Aw ? 1 : 0;
 }
 
@@ -1405,6 +1405,7 @@ size_t ia_db_cov_bytes(void) { return (size_t)(R16_LD * R16_LD + COV_BLOCKS * CO
 
 int ia_db_cov(const IaSrcLevel *src, long row0, long nrows, const double *center, double *cov, void *stream) {
     IA_ARG(src && center && cov && nrows > 0 && row0 >= 0, "ia_db_cov: bad args");
+    IA_SRC_NA(*src, "ia_db_cov");
     IA_ARG(row0 + nrows <= (long)src->nAp * src->Ah * src->Aw, "ia_db_cov: rows out of range");
     hipStream_t st = S(stream);
     const DbSrc d = make_dbsrc(*src);
@@ -1424,6 +1425,7 @@ int ia_db_cov(const IaSrcLevel *src, long row0, long nrows, const double *center
 int ia_db_build_rot(const IaSrcLevel *src, long row0, long nrows, const double *center, const float *rot,
                     float *amax, void *dbr, void *stream) {
     IA_ARG(src && center && rot && amax && dbr && nrows > 0 && row0 >= 0, "ia_db_build_rot: bad args");
+    IA_SRC_NA(*src, "ia_db_build_rot");
     IA_ARG(row0 + nrows <= (long)src->nAp * src->Ah * src->Aw, "ia_db_build_rot: rows out of range");
     IA_ARG(row0 + nrows < (1L << 31), "ia_db_build_rot: rows past 2^31");
     hipStream_t st = S(stream);
@@ -1458,6 +1460,7 @@ size_t ia_db_rotk_bytes(long nrows) { return nrows > 0 && RK_BUILT ? rk_bytes(nr
 int ia_db_rotk_applies(const IaSrcLevel *src, long row0, long nrows) {
     // single-shard strip-order levels of the fused strip kernel at or above the row threshold
     if (!RK_BUILT || !ia_db_rot_applies(src, row0, nrows)) return 0;
+    if (src_pairs(*src)) return 0;   // (the compact waves' exact stage reads the image form)
     if (row0 != 0 || nrows != (long)src->nAp * src->Ah * src->Aw) return 0;
     return compact_level(make_dbsrc(*src), db_stage_map(row0, nrows, src->Aw, src->Ah), nrows) &&
                    db_seg_rows(nrows) >= 128 ? 1 : 0;
@@ -1467,6 +1470,8 @@ int ia_db_build_rotk(const IaSrcLevel *src, long row0, long nrows, const double 
                      const float *amax, void *dbk, void *stream) {
     IA_ARG(src && center && rot && amax && dbk && nrows > 0 && row0 >= 0, "ia_db_build_rotk: bad args");
     IA_ARG(RK_BUILT, "ia_db_build_rotk: this build has no compact form");
+    IA_SRC_NA(*src, "ia_db_build_rotk");
+    IA_ARG(!src_pairs(*src), "ia_db_build_rotk: no compact form for training pairs (nA > 1)");
     IA_ARG(row0 + nrows <= (long)src->nAp * src->Ah * src->Aw, "ia_db_build_rotk: rows out of range");
     IA_ARG(row0 + nrows < (1L << 31), "ia_db_build_rotk: rows past 2^31");
     // (k_db_build_rotk's per-wave R_j: a wave's 64 rows lie in one segment; the compact waves' exact
@@ -1502,6 +1507,7 @@ static int diag_screen16r(const char *who, bool compact, const IaSrcLevel *src, 
                           void *stream) {
     IA_ARG(src && dbr && rot && amax && center && q64 && q16 && nq && nsk && segmin && M > 0,
            std::string(who) + ": bad args");
+    IA_SRC_NA(*src, who);
     hipStream_t st = S(stream);
     int rc = launch_query_rows_r16(q64, M, center, rot, amax, nq, nsk, reinterpret_cast<_Float16 *>(q16), st, compact);
     if (rc) return rc;

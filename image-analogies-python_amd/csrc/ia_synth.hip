@@ -427,6 +427,8 @@ int level_plan(const IaSynthArgs &a, int K, bool sim, LevelPlan *p) {
     LevelPlan &l = *p;
     l = LevelPlan{};
     l.form = -1;
+    IA_SRC_NA(a.src, "ia_synth_level");
+    l.pairs = src_pairs(a.src);
     l.nranks = comm_nranks(a.comm);
     // the device-side exchange: the exact stage (or the fused kernel) publishes, no RCCL call
     l.peer = a.comm && comm_peer_mcap(a.comm) > 0;
@@ -628,6 +630,7 @@ struct LevelRun {
         LJob J{};
         J.A_sm = a->src.A_sm; J.A_lg = a->src.A_lg; J.Ap_sm = a->src.Ap_sm; J.Ap_lg = a->src.Ap_lg;
         J.A_hs = a->src.A_hs; J.A_ws = a->src.A_ws; J.Ah = a->src.Ah; J.Aw = a->src.Aw;
+        J.pairs = src_pairs(a->src) ? 1 : 0;
         J.B_sm = a->B_sm; J.B_lg = a->B_lg; J.Bp_sm = a->Bp_sm; J.Bp_lg = a->Bp_lg;
         J.B_hs = a->B_hs; J.B_ws = a->B_ws; J.H = H; J.W = W;
         lsh_job_tables(a->lsh, a->nrows, &J);
@@ -710,7 +713,7 @@ struct LevelRun {
             IA_ARG(b.H == a->H && b.W == a->W && b.nrows == a->nrows && b.N_total == a->N_total &&
                        b.row0 == a->row0 && b.B_hs == a->B_hs && b.B_ws == a->B_ws &&
                        b.src.Ah == a->src.Ah && b.src.Aw == a->src.Aw && b.src.A_hs == a->src.A_hs &&
-                       b.src.A_ws == a->src.A_ws && b.src.nAp == a->src.nAp &&
+                       b.src.A_ws == a->src.A_ws && b.src.nAp == a->src.nAp && b.src.nA == a->src.nA &&
                        !b.comm == !a->comm && !b.lsh == !a->lsh && !b.dbi == !a->dbi &&
                        !b.dbg_px == !a->dbg_px,
                    "ia_synth_levels_batch: the jobs of a batch must have identical shapes and forms");
@@ -915,7 +918,7 @@ int ia_level_resources(const IaSynthArgs *a, int *out) {
     int rc = level_plan(*a, 1, false, &p);
     if (rc) return rc;
     hipFuncAttributes f{}, sc{};
-    if (p.xw) rc = xwave_attributes(XwVariant{p.form, false, p.r16, false, false}, &f);
+    if (p.xw) rc = xwave_attributes(XwVariant{p.form, false, p.r16, false, false, p.pairs}, &f);
     else IA_HIP(hipFuncGetAttributes(&f, reinterpret_cast<const void *>(&k_peer_finish)));
     if (rc) return rc;
     rc = p.r16 ? screen_resources_r16(&sc) : screen16_attributes(a->dbi != nullptr, &sc);
@@ -1226,7 +1229,7 @@ int ia_synth_levels_batch(const IaSynthArgs *levels, int n, int K, void *stream)
 #define IA_SAME(field) IA_ARG(b.field == c.field, "ia_synth_levels_batch: jobs sharing a database differ in " #field)
                 IA_SAME(db); IA_SAME(dbi); IA_SAME(dbr); IA_SAME(dbk); IA_SAME(rot); IA_SAME(center); IA_SAME(amax);
                 IA_SAME(row0); IA_SAME(nrows);
-                IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg);
+                IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg); IA_SAME(src.nA);
 #undef IA_SAME
             }
         }
@@ -1250,6 +1253,7 @@ int ia_synth_levels_lsh_batch(const IaSynthArgs *levels, int n, int K, void *str
 #define IA_SAME(field) IA_ARG(b.field == a.field, who + ": the jobs of an lsh batch differ in " #field)
             IA_SAME(H); IA_SAME(W); IA_SAME(B_hs); IA_SAME(B_ws);
             IA_SAME(src.Ah); IA_SAME(src.Aw); IA_SAME(src.A_hs); IA_SAME(src.A_ws); IA_SAME(src.nAp);
+            IA_SAME(src.nA);
             IA_SAME(nrows); IA_SAME(lsh->L); IA_SAME(lsh->k);
 #undef IA_SAME
             {
@@ -1272,7 +1276,7 @@ int ia_synth_levels_lsh_batch(const IaSynthArgs *levels, int n, int K, void *str
                 if (c.lsh->mem != b.lsh->mem) continue;
 #define IA_SAME(field) IA_ARG(b.field == c.field, who + ": jobs sharing lsh->mem differ in " #field)
                 IA_SAME(lsh->proj); IA_SAME(lsh->w); IA_SAME(center);
-                IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg);
+                IA_SAME(src.A_sm); IA_SAME(src.A_lg); IA_SAME(src.Ap_sm); IA_SAME(src.Ap_lg); IA_SAME(src.nA);
 #undef IA_SAME
                 break;   // (p agrees with the group's earlier jobs already)
             }
@@ -1300,6 +1304,7 @@ int ia_synth_levels_lsh_batch(const IaSynthArgs *levels, int n, int K, void *str
 int ia_batch_groups(const IaSynthArgs *level_jobs, int K, int *group_of_job) {
     IA_ARG(level_jobs && group_of_job, "ia_batch_groups: bad args");
     IA_ARG(K >= 1 && K <= IA_BATCH_MAX, "ia_batch_groups: K out of range (1 .. 128)");
+    for (int k = 0; k < K; ++k) IA_SRC_NA(level_jobs[k].src, "ia_batch_groups");
     return batch_groups(level_jobs, K, group_of_job);
 }
 

@@ -331,8 +331,11 @@ __device__ __forceinline__ void xw_next_query(const XArgs &a, int i, int y, int 
 #ifndef IA_XWAVE_OCC
 #define IA_XWAVE_OCC 2   // workgroups per CU k_xwave is built for (3: 168 VGPRs and 240-448 B of spills, c1 +8 %, c3 +11 %)
 #endif
-template <bool IMG, bool BATCH>
+// PAIRS: a row-form level of training pairs (DbSrc::pairs): a row's A half comes from its own A
+// image, stacked like the A' images
+template <bool IMG, bool BATCH, bool PAIRS = false>
 __global__ __launch_bounds__(256, IA_XWAVE_OCC) void k_xwave(XArgs a0) {
+    static_assert(!(IMG && PAIRS), "the image form holds one A");
     __shared__ __attribute__((aligned(16))) char sa_raw[BATCH ? sizeof(XArgs) : 16];
     XArgs &sa = *reinterpret_cast<XArgs *>(sa_raw);
     if constexpr (BATCH) {
@@ -373,6 +376,7 @@ __global__ __launch_bounds__(256, IA_XWAVE_OCC) void k_xwave(XArgs a0) {
     const FinishArgs &f = a.f;
     const DbSrc &src = a.src;
     const int t = f.t, W = f.W;
+    constexpr bool pairs = PAIRS;   // (launch_xwave: the instance follows a.src.pairs)
     // an R16 level (a.rot): wave 0 copies the rotation into the pool once the exact stage is
     // done with it, for the next query row (as k_xstrip), 64 doubles of scratch after it
     static_assert(R16_ROT_B + 64 * 8 <= (POOL > RESB ? POOL : RESB), "the rotation fits the pool");
@@ -500,7 +504,9 @@ __global__ __launch_bounds__(256, IA_XWAVE_OCC) void k_xwave(XArgs a0) {
                 const int pr = __builtin_amdgcn_readlane(c_r, c), pc = __builtin_amdgcn_readlane(c_c, c);
                 const int pi = __builtin_amdgcn_readlane(c_i, c);
                 int rr, cc;
-                const double *fp = feat_addr_v(As, Al, Ps + (long)pi * hws, Pl + (long)pi * hw, fh, fw, chh, cww,
+                const long os = (long)pi * hws, ol = (long)pi * hw;
+                const double *fp = feat_addr_v(As + (pairs ? os : 0), Al + (pairs ? ol : 0), Ps + os, Pl + ol,
+                                               fh, fw, chh, cww,
                                                pr, pc, lane < IA_D ? lane : 0, rr, cc);
                 dma_f64(fp, true, clo + c * 64, chi + c * 64);
             }
@@ -623,8 +629,9 @@ __global__ __launch_bounds__(256, IA_XWAVE_OCC) void k_xwave(XArgs a0) {
                     const int ri = __shfl(li, j), rr = __shfl(lr_, j), rc = __shfl(lc, j);
                     const long rg = __shfl(lg, j);
                     int r2, c2;
-                    const double *fp = feat_addr_v(src.A.sm, src.A.lg, src.Ap.sm + (long)ri * src.hws,
-                                                   src.Ap.lg + (long)ri * src.hw, src.A.h, src.A.w, src.A.hs,
+                    const long os = (long)ri * src.hws, ol = (long)ri * src.hw;
+                    const double *fp = feat_addr_v(src.A.sm + (pairs ? os : 0), src.A.lg + (pairs ? ol : 0),
+                                                   src.Ap.sm + os, src.Ap.lg + ol, src.A.h, src.A.w, src.A.hs,
                                                    src.A.ws, rr, rc, lane < IA_D ? lane : 0, r2, c2);
                     dma_f64(lane == IA_D ? src.Ap.lg + rg : fp, true, rw + j * 128, rw + j * 128 + 64);
                 }
@@ -1708,9 +1715,9 @@ __global__ __launch_bounds__(256, BATCH ? IA_XSTRIP_BOCC : 3) void k_xstrip(XArg
                 }
                 wb.val = wdb[XS_FP + fb];
             } else {
-                ImgPair ap;
+                ImgPair ai, ap;   // (the strip form is one A's: src.A, launch_xwave checks)
                 int r, c;
-                src.locate(bi, ap, r, c);
+                src.locate(bi, ai, ap, r, c);
                 int rr, cc;
                 const double *fp = feat_addr(src.A, ap, r, c, lane < IA_D ? lane : 0, rr, cc);
                 if (lane < IA_D) {
@@ -1804,10 +1811,13 @@ const void *xwave_kernel(XwVariant v) {
         {{XW_STRIP, true, false, false, false}, (const void *)&k_xstrip<true, false>},
         {{XW_IMG, true, false, false, false}, (const void *)&k_xwave<true, true>},
         {{XW_ROWS, true, false, false, false}, (const void *)&k_xwave<false, true>},
+        {{XW_ROWS, false, false, false, false, true}, (const void *)&k_xwave<false, false, true>},
+        {{XW_ROWS, true, false, false, false, true}, (const void *)&k_xwave<false, true, true>},
     };
     if (v.form != XW_STRIP) v.rot = false;   // (k_xwave takes the R16 bound at run time)
     for (const auto &e : built)
-        if (e.v.form == v.form && e.v.batch == v.batch && e.v.rot == v.rot && e.v.cmp == v.cmp && e.v.split == v.split)
+        if (e.v.form == v.form && e.v.batch == v.batch && e.v.rot == v.rot && e.v.cmp == v.cmp && e.v.split == v.split &&
+            e.v.pairs == v.pairs)
             return e.f;
     set_error("xwave_kernel: this instance of the fused kernel is not built");
     return nullptr;
@@ -1827,6 +1837,8 @@ int launch_xwave(const XArgs &a, int nblocks, XwVariant v, hipStream_t st, int n
     IA_ARG(v.form != XW_STRIP || (a.smap.W > 0 && xstrip_applies(a.src) && a.seg_rows >= 128 && a.seg_rows <= 512),
            "launch_xwave: the strip form needs a strip-order image-form level");
     IA_ARG(v.form != XW_STRIP || v.rot == (a.rot != nullptr), "launch_xwave: the strip form and its rotation disagree");
+    IA_ARG(v.form == XW_ROWS || !a.src.pairs, "launch_xwave: training pairs (nA > 1) run the row form");
+    IA_ARG(v.pairs == (a.src.pairs != 0), "launch_xwave: the instance and the level disagree about training pairs");
     IA_ARG(v.cmp == (a.restc != nullptr) && (!v.cmp || (RK_BUILT && a.rmax && a.q16)),
            "launch_xwave: a compact wave is one job of an R16 strip level");
     IA_ARG(v.split == (a.xbox != nullptr) && (!v.split || (!a.f.px.nranks && a.nseg <= XS_SEG_MASK + 1)),

@@ -205,14 +205,20 @@ def pipeline_default():
     return os.environ.get('IA_PIPELINE', '1') != '0'
 
 
-def _src_level3(A_sm, A_lg, Ap_sm, Ap_lg):
-    """IaSrcLevel over 3-channel device tensors (A_*: (h, w, 3); Ap_*: (nAp, h, w, 3))."""
+def _src_level3(A_sm, A_lg, Ap_sm, Ap_lg, nA=1):
+    """IaSrcLevel over 3-channel device tensors (A_*: (h, w, 3); Ap_*: (nAp, h, w, 3)).  nA = nAp
+    > 1: training pairs, A_* stacked (nA, h, w, 3) like Ap_* (stated by the caller, as
+    _ia.src_level's)."""
+    nA = int(nA)
+    if nA not in (1, int(Ap_lg.shape[0])) or (nA > 1 and tuple(A_lg.shape) != tuple(Ap_lg.shape)):
+        raise ValueError('nA must be 1 (one A) or the number of A\' images (A stacked like A\')')
     src = _ia.IaSrcLevel()
     src.A_sm, src.A_lg, src.Ap_sm, src.Ap_lg = (_ia.ptr(A_sm).value, _ia.ptr(A_lg).value,
                                                 _ia.ptr(Ap_sm).value, _ia.ptr(Ap_lg).value)
-    src.A_hs, src.A_ws = A_sm.shape[:2]
-    src.Ah, src.Aw = A_lg.shape[:2]
+    src.A_hs, src.A_ws = Ap_sm.shape[1:3]
+    src.Ah, src.Aw = Ap_lg.shape[1:3]
     src.nAp = Ap_lg.shape[0]
+    src.nA = nA
     return src
 
 
@@ -221,10 +227,11 @@ def _db3_level(A_pyr, Ap_pyr_list, level, row_range=None):
     (row0, nrows)).  row_range: None (all N rows) or the (row0, nrows) of a sharded level's
     rank, whose buffer then holds those rows alone (tiles, centre and bound its own)."""
     lib = _ia.lib()
-    A_sm, A_lg = A_pyr[level - 1].contiguous(), A_pyr[level].contiguous()
+    A_sm, A_lg, nA = algorithms.a_level(A_pyr, len(Ap_pyr_list), level)   # (pairs: stacked like A')
+    A_sm, A_lg = A_sm.contiguous(), A_lg.contiguous()
     Ap_sm = torch.stack([p[level - 1] for p in Ap_pyr_list]).contiguous()
     Ap_lg = torch.stack([p[level] for p in Ap_pyr_list]).contiguous()
-    src = _src_level3(A_sm, A_lg, Ap_sm, Ap_lg)
+    src = _src_level3(A_sm, A_lg, Ap_sm, Ap_lg, nA)
     N = src.nAp * src.Ah * src.Aw
     row0, nrows = (0, N) if row_range is None else row_range
     db3 = torch.empty(lib.ia_db3_bytes(nrows) // 8, dtype=torch.float64, device=A_lg.device)
@@ -445,11 +452,12 @@ def synthesize3_batch_dev(jobs, max_levels, ks, weights, debug=False, check=True
 def db_groups(jobs):
     """The DB group of each job of a batch (colour or luminance), numbered in job order: two
     jobs are in one group when their A pyramids and all their A' pyramids are the same tensors
-    level by level (data_ptr, shape and stride; the same number of A' images).  Identity only: equal contents
+    level by level (data_ptr, shape and stride; the same number of A and of A' images).  Identity only: equal contents
     in distinct tensors are distinct groups (multi_main aliases such pyramids first)."""
     def ident(A_pyr, Ap_list):
-        return tuple(tuple((p.data_ptr(), tuple(p.shape), p.stride()) for p in pyr)
-                     for pyr in [A_pyr] + list(Ap_list))
+        As = algorithms.a_pyramids(A_pyr)
+        return (len(As),) + tuple(tuple((p.data_ptr(), tuple(p.shape), p.stride()) for p in pyr)
+                                  for pyr in As + list(Ap_list))
     seen = {}
     return [seen.setdefault(ident(A_pyr, Ap_list), len(seen)) for A_pyr, Ap_list, _, _ in jobs]
 
@@ -777,38 +785,81 @@ def _read(fname):
     return img[..., :3] if img.ndim == 3 and img.shape[2] == 4 else img
 
 
+def a_images(A, nAp):
+    """(A images, pairs): A is one image (shared by every A' image: pairs False), or a list or
+    tuple of images or file names, one per A' image (training pairs (A_i, A'_i)); a 1-element
+    list is the single A.  ValueError for any other count."""
+    if not isinstance(A, (list, tuple)):
+        return [A], False
+    if len(A) == 1:
+        return [A[0]], False
+    if len(A) != nAp:
+        raise ValueError('%d A images for %d A\' images: training pairs need one A per A\'' % (len(A), nAp))
+    return list(A), True
+
+
+def _read_A(A_fname, nAp):
+    """The decoded A image, or for a list or tuple of len(Ap_fname_list) names (training pairs)
+    the list of them; the count is checked before any file is read (a_images)."""
+    names, pairs = a_images(A_fname, nAp)
+    return [_read(f) for f in names] if pairs else _read(names[0])
+
+
 def setup_dev(A_orig, Ap_orig_list, B_orig, c):
     """Numeric part of img_setup on device, from already-decoded images.
-    Returns device (A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, color_pyr_list) and sets c.*."""
-    assert len(A_orig.shape) == len(B_orig.shape)
-    if not c.convert and np.ndim(A_orig) == 3:
+    Returns device (A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, color_pyr_list) and sets c.*.
+    A_orig: one image, or a list of len(Ap_orig_list) images of one shape: training pairs
+    (A_i, A'_i), and A_pyr is then the list of their pyramids.  Per pair: the 0-1 scale rule
+    takes each A image by itself, remap_lum remaps pair i with A_i's own statistics
+    (remap_luminance_dev(A_i, [A'_i], B)) and AB_weight scales every A_i; the A' scale is the
+    one rule it always was.  A length mismatch or differing shapes raise ValueError before any
+    device work."""
+    A_list, pairs = a_images(A_orig, len(Ap_orig_list))
+    for A_i in A_list:
+        if np.shape(A_i) != np.shape(A_list[0]):
+            raise ValueError('training pairs need A images of one shape: %s and %s'
+                             % (np.shape(A_list[0]), np.shape(A_i)))
+    if pairs:
+        for Ap in Ap_orig_list:
+            if np.shape(Ap) != np.shape(A_list[0]):
+                raise ValueError('training pairs need A and A\' images of one shape: %s and %s'
+                                 % (np.shape(A_list[0]), np.shape(Ap)))
+    assert len(A_list[0].shape) == len(B_orig.shape)
+    if not c.convert and np.ndim(A_list[0]) == 3:
         if c.remap_lum:
             raise ValueError('remap_lum requires convert (config.py:11-12)')
     dev = _ia.require_device()
     for Ap in Ap_orig_list:
-        assert A_orig.shape == Ap.shape
-    # scale to [0, 1]; the A' scale comes from the first row of the LAST A'
-    # (image_analogies.py:32-37 reads Ap_orig[0] after the loading loop)
+        assert A_list[0].shape == Ap.shape
+    # scale to [0, 1] (each A image by its own maximum); the A' scale comes from the first row of
+    # the LAST A' (image_analogies.py:32-37 reads Ap_orig[0] after the loading loop)
     scales = [255. if np.max(x) > 1.0 else 1.0
-              for x in (A_orig, B_orig, Ap_orig_list[-1][0])]
+              for x in (B_orig, Ap_orig_list[-1][0])]
+    a_scales = [255. if np.max(x) > 1.0 else 1.0 for x in A_list]
     up = lambda x: torch.as_tensor(np.ascontiguousarray(x)).to(dev)  # noqa: E731
     color_B = None
     if c.convert:
-        _, A = ip.rgb_to_yiq_dev(up(A_orig), scales[0], want_yiq=False)
-        B_yiq, B = ip.rgb_to_yiq_dev(up(B_orig), scales[1], want_yiq=True)
-        Ap_list = [ip.rgb_to_yiq_dev(up(x), scales[2], want_yiq=False)[1] for x in Ap_orig_list]
+        As = [ip.rgb_to_yiq_dev(up(x), sc, want_yiq=False)[1] for x, sc in zip(A_list, a_scales)]
+        B_yiq, B = ip.rgb_to_yiq_dev(up(B_orig), scales[0], want_yiq=True)
+        Ap_list = [ip.rgb_to_yiq_dev(up(x), scales[1], want_yiq=False)[1] for x in Ap_orig_list]
         color_B = B_yiq
     else:
-        A = ip.scale_dev(up(A_orig), scales[0])
-        B = ip.scale_dev(up(B_orig), scales[1])
-        Ap_list = [ip.scale_dev(up(x), scales[2]) for x in Ap_orig_list]
-    if c.remap_lum:
-        A, Ap_list = ip.remap_luminance_dev(A, Ap_list, B)
+        As = [ip.scale_dev(up(x), sc) for x, sc in zip(A_list, a_scales)]
+        B = ip.scale_dev(up(B_orig), scales[0])
+        Ap_list = [ip.scale_dev(up(x), scales[1]) for x in Ap_orig_list]
+    if c.remap_lum and pairs:
+        remapped = [ip.remap_luminance_dev(A_i, [Ap_i], B) for A_i, Ap_i in zip(As, Ap_list)]
+        As, Ap_list = [r[0] for r in remapped], [r[1][0] for r in remapped]
+    elif c.remap_lum:
+        A0, Ap_list = ip.remap_luminance_dev(As[0], Ap_list, B)
+        As = [A0]
     levels = getattr(c, 'levels', None)
     B_orig_pyr = None if c.init_rand else ip.gaussian_pyramid_dev(B, c.n_sm, levels)
-    A, B = ip.compress_values_dev(A, B, c.AB_weight)
+    A, B = ip.compress_values_dev(As[0], B, c.AB_weight)
+    As = [A] + [ip.compress_dev(A_i, c.AB_weight) for A_i in As[1:]]
     c.num_ch, c.padding_sm, c.padding_lg, c.weights = setup_vars(A)
-    A_pyr = ip.gaussian_pyramid_dev(A, c.n_sm, levels)
+    A_pyrs = [ip.gaussian_pyramid_dev(A_i, c.n_sm, levels) for A_i in As]
+    A_pyr = A_pyrs[0]
     B_pyr = ip.gaussian_pyramid_dev(B, c.n_sm, levels)
     Ap_pyr_list = [ip.gaussian_pyramid_dev(Ap, c.n_sm, levels) for Ap in Ap_list]
     if c.convert:
@@ -824,20 +875,23 @@ def setup_dev(A_orig, Ap_orig_list, B_orig, c):
     init = ip.initialize_Bp([p.cpu() for p in (B_pyr if c.init_rand else B_orig_pyr)],
                             c.init_rand, getattr(c, 'seed', None))
     Bp_pyr = [torch.as_tensor(np.ascontiguousarray(x)).to(dev) for x in init]
-    return A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, color_pyr_list
+    return (A_pyrs if pairs else A_pyr), Ap_pyr_list, B_pyr, Bp_pyr, color_pyr_list
 
 
 def img_setup(A_fname, Ap_fname_list, B_fname, out_path, c):
     """Read, convert, remap, compress and build pyramids (image_analogies.py:17-94).
-    Returns numpy pyramids like the reference."""
+    Returns numpy pyramids like the reference (A_fname a list of len(Ap_fname_list) names:
+    training pairs, and the first entry is the list of the A pyramids)."""
+    a_images(A_fname, len(Ap_fname_list))   # (a bad A count: ValueError before anything is created)
     if not os.path.exists(out_path):
         os.makedirs(out_path)
-    A_orig, B_orig = _read(A_fname), _read(B_fname)
+    A_orig, B_orig = _read_A(A_fname, len(Ap_fname_list)), _read(B_fname)
     Ap_orig_list = [_read(f) for f in Ap_fname_list]
     dev_out = setup_dev(A_orig, Ap_orig_list, B_orig, c)
     to_np = lambda pyr: [p.cpu().numpy() for p in pyr]  # noqa: E731
     A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, color_pyr_list = dev_out
-    return (to_np(A_pyr), [to_np(p) for p in Ap_pyr_list], to_np(B_pyr), to_np(Bp_pyr),
+    A_np = [to_np(p) for p in A_pyr] if isinstance(A_pyr[0], (list, tuple)) else to_np(A_pyr)
+    return (A_np, [to_np(p) for p in Ap_pyr_list], to_np(B_pyr), to_np(Bp_pyr),
             [to_np(p) for p in color_pyr_list], c)
 
 
@@ -927,16 +981,22 @@ def image_analogies_main(A_fname, Ap_fname_list, B_fname, out_path, c, debug=Fal
     sharded level (level_exchanges), released before returning.  comm may also be
     exchanges the caller made (then pass rank and nranks).  Every rank ends with the same
     B' (the exchange is deterministic); only rank 0 writes the output files and prints.
-    To spread independent runs over GPUs instead (the multi_script loop) use multi_main."""
+    To spread independent runs over GPUs instead (the multi_script loop) use multi_main.
+
+    Training pairs: A_fname a list or tuple of len(Ap_fname_list) names pairs A_fname[i] with
+    Ap_fname_list[i] (a row of the level database is then [full(A_i) | half(A'_i)]); a
+    1-element list is the single A.  A length mismatch or images of differing shapes raise
+    ValueError before any device work (setup_dev has the per-pair setup rules)."""
     r0, w0 = dist_world()
     rank = r0 if rank is None else rank
     nranks = (w0 if comm is not None else 1) if nranks is None else nranks
     lead = rank == 0
     say = print if lead else (lambda *a, **kw: None)
     begin_time = start_time = time.time()
+    a_images(A_fname, len(Ap_fname_list))   # (a bad A count: ValueError before anything is created)
     if lead and not os.path.exists(out_path):
         os.makedirs(out_path)
-    A_orig, B_orig = _read(A_fname), _read(B_fname)
+    A_orig, B_orig = _read_A(A_fname, len(Ap_fname_list)), _read(B_fname)
     Ap_orig_list = [_read(f) for f in Ap_fname_list]
     A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, color_pyr_list = setup_dev(A_orig, Ap_orig_list,
                                                                   B_orig, c)
@@ -996,11 +1056,13 @@ def write_outputs(res, Bp_pyr, color_pyr_list, c, out_path, debug=False, outputs
 
 def _run_key(c, A_pyr, Ap_pyr_list, B_pyr):
     """What the runs of one batch agree on (multi_main): channel count, levels, every pyramid
-    shape, the number of A' images, and the matcher: None for the exact one, else the LSH
+    shape, the number of A' images and of A images (1, or one per A' image: training pairs), and
+    the matcher: None for the exact one, else the LSH
     parameter set (tables, hashes, width, seed) as a hashable, on which runs agree exactly."""
-    shapes = tuple(tuple(p.shape) for pyr in (A_pyr, B_pyr) for p in pyr)
+    As = algorithms.a_pyramids(A_pyr)
+    shapes = tuple(tuple(p.shape) for pyr in As + [B_pyr] for p in pyr)
     lsh = algorithms.lsh_params(c)
-    return (c.num_ch, c.max_levels, shapes, len(Ap_pyr_list),
+    return (c.num_ch, c.max_levels, shapes, len(Ap_pyr_list), len(As),
             None if lsh is None else tuple(sorted(lsh.items())))
 
 
@@ -1026,9 +1088,10 @@ def _alias_pyramids(same):
         A_pyr, Ap_list = r[3][0], r[3][1]
         for e in same[:i]:
             A0, Ap0 = e[3][0], e[3][1]
-            if e[5] != r[5] or A0 is A_pyr or len(Ap0) != len(Ap_list):
+            As0, As = algorithms.a_pyramids(A0), algorithms.a_pyramids(A_pyr)
+            if e[5] != r[5] or A0 is A_pyr or len(Ap0) != len(Ap_list) or len(As0) != len(As):
                 continue
-            pairs = list(zip(A0, A_pyr)) + [xy for p0, p in zip(Ap0, Ap_list) for xy in zip(p0, p)]
+            pairs = [xy for p0, p in zip(As0 + list(Ap0), As + list(Ap_list)) for xy in zip(p0, p)]
             if all(x.shape == y.shape and torch.equal(x, y) for x, y in pairs):
                 colour = Ap0 if r[3][4] is Ap_list else r[3][4]   # (convert=False: the A' pyramids)
                 r[3] = (A0, Ap0) + tuple(r[3][2:4]) + (colour,)
@@ -1051,14 +1114,18 @@ def _multi_batch(group, c, debug):
         cj = types.SimpleNamespace(**{f: v for f, v in vars(c).items() if not f.startswith('__')})
         for key, val in (run[4] if len(run) > 4 else {}).items():
             setattr(cj, key, val)
+        a_images(A_fname, len(Ap_fname_list))   # (a bad A count: ValueError before anything is created)
         if not os.path.exists(out_path):
             os.makedirs(out_path)
-        pyrs = setup_dev(_read(A_fname), [_read(f) for f in Ap_fname_list], _read(B_fname), cj)
+        pyrs = setup_dev(_read_A(A_fname, len(Ap_fname_list)), [_read(f) for f in Ap_fname_list],
+                         _read(B_fname), cj)
         save_metadata(out_path, ['A_fname', 'Ap_fname_list', 'B_fname', 'c.convert', 'c.remap_lum',
                                  'c.init_rand', 'c.AB_weight', 'c.k'],
                       [A_fname, Ap_fname_list, B_fname, cj.convert, cj.remap_lum, cj.init_rand,
                        cj.AB_weight, cj.k])
-        named = (A_fname, tuple(Ap_fname_list), cj.convert, cj.remap_lum, cj.AB_weight,
+        # (a list of A names: training pairs; the names and their count are part of the key)
+        named = (tuple(A_fname) if isinstance(A_fname, (list, tuple)) else A_fname,
+                 tuple(Ap_fname_list), cj.convert, cj.remap_lum, cj.AB_weight,
                  getattr(cj, 'levels', None), cj.n_sm)
         ready.append([j, out_path, cj, pyrs, _run_key(cj, pyrs[0], pyrs[1], pyrs[2]), named])
     results = {}

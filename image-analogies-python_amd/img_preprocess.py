@@ -112,8 +112,13 @@ def remap_luminance(A, Ap_list, B):
     return A2.cpu().numpy(), [x.cpu().numpy() for x in Ap2]
 
 
+def compress_dev(X, ratio):
+    """One image times AB_weight (the further A images of training pairs)."""
+    return _axpb_dev(X, 0, ratio)
+
+
 def compress_values_dev(A, B, ratio):
-    return _axpb_dev(A, 0, ratio), _axpb_dev(B, 0, ratio)
+    return compress_dev(A, ratio), compress_dev(B, ratio)
 
 
 def compress_values(A, B, ratio):

@@ -42,10 +42,20 @@ int ia_version(void);
 
 /* One pyramid level pair of the A / A' database (algorithms.py:50-70 inputs).
  * A_sm/A_lg: A at levels l-1 (A_hs x A_ws) and l (Ah x Aw), fp64.
- * Ap_sm/Ap_lg: nAp A' images stacked contiguously with the same shapes. */
+ * Ap_sm/Ap_lg: nAp A' images stacked contiguously with the same shapes.
+ * nA: the number of A images.  0 or 1: one A for every A' image (row ix of the level's
+ * database is [full(A) at p | half(A'_i) at p], ix = (i * Ah + r) * Aw + c); nA == nAp:
+ * training pairs (A_i, A'_i), A_sm / A_lg hold nA images stacked contiguously like
+ * Ap_sm / Ap_lg and the row is [full(A_i) at p | half(A'_i) at p].  Any other value is
+ * IA_E_ARG (the message names nA) from every entry that takes an IaSrcLevel or an
+ * IaSynthArgs.  Levels of pairs have no image form (ia_db_image_bytes returns 0,
+ * ia_db_build_image IA_E_ARG) and no compact rotated database (ia_db_rotk_applies 0):
+ * they run from the split-f16 rows, with the R16 screen where ia_db_rot_applies.
+ * The field fills the struct's tail padding: zero-initialised callers keep one A. */
 typedef struct {
     const double *A_sm, *A_lg, *Ap_sm, *Ap_lg;
     int A_hs, A_ws, Ah, Aw, nAp;
+    int nA;
 } IaSrcLevel;
 
 /* ---- a1/a2: img_preprocess.py:6-13 convert_to_YIQ (+ image_analogies.py:32-50 scale).
