@@ -15,9 +15,16 @@
 // one LDS-only barrier per stage) and every byte fetched feeds the block's 4 waves; the
 // stage's (query block, row block) chains are cut into 4 equal runs (chain balance), each
 // chain's MFMAs run back to back and its running-minimum fold is taken a few chains later
-// (no MFMA -> VALU hazard pads), interleaved with the later chains' MFMAs; minima staged in
-// LDS 2 segments at a time (the compact form: 8, a whole part of the finest levels, so that a
-// query's minima leave in runs of 32 B).
+// (no MFMA -> VALU hazard pads), interleaved with the later chains' MFMAs, as one dependent
+// chain of v_min3_f32 (fold4: two per 16x16x32 chain, which its MFMA's free vector issue
+// covers; a tree costs three); at a segment's close the 16x16x32 forms reduce four query blocks
+// at a time over the lane groups with v_permlane16_swap / v_permlane32_swap and one 64-lane
+// ds_min_i32 (close_blocks_s16); minima staged in LDS 2 segments at a time (the compact form:
+// 8, a whole part of the finest levels, so that a query's minima leave in runs of 32 B, two
+// 16-byte stores by two lanes of different wave halves).  k_screen16r and k_screen16rs keep
+// the tree fold, a ds_bpermute close per block and a per-element flush (k_screen16r's
+// instructions and registers are pinned, tests/test_lum_shared_host.py, and k_screen16rs is its
+// copy); k_screen16c and k_screen16w take the new fold and close.
 #include "ia_internal.h"
 #include "ia_rot16.h"
 #include "../../include/ia_diag.h"
@@ -56,6 +63,12 @@ constexpr int R16_RING = IA_R16_RING;
 #define IA_R16_SPC 2
 #endif
 constexpr int SPC_STAGE = IA_R16_SPC;   // segments of minima staged in LDS at a time
+// the compact form's flush of a full group of staged segments: 1 takes it at the compile-time
+// count (no division by the group's length) with one 16-byte store per lane (4 staged segments
+// of a query: 16 aligned bytes of segmin); 0 is the per-element loop every group took before
+#ifndef IA_R16_FLUSH
+#define IA_R16_FLUSH 1
+#endif
 // The compact form (k_screen16c) has its own stage geometry (DESIGN.md §4d "compact"): tiles per
 // stage (4 or 8: 8 or 16 KiB; a level whose segments are no whole number of 8-tile stages takes
 // 4), stage buffers, segments of minima staged at a time, blocks per CU (A/B builds).  Measured
@@ -219,6 +232,24 @@ __device__ __forceinline__ void r16_stage(const half8 *sb, const half8 (&bq)[NS]
 // block's two operand reads serve all its chains.  Output: lane l holds rows 4 (l / 16) .. + 3
 // of query l % 16, folded per lane, reduced over the 4 lane groups at each segment close.
 typedef float floatx4 __attribute__((ext_vector_type(4)));
+// a chain's four values into its running minimum as ONE dependent chain: two v_min3_f32 (a tree,
+// min(min(mn, min(x0, x1)), min(x2, x3)), is v_min, v_min, v_min3, and a 16x16x32 MFMA leaves the
+// SIMD's vector issue 8 of its 16 cycles: two VALU fit, three do not).  Finite values
+// (-fno-honor-nans): the same minimum bit for bit in any order.  IA_R16_FOLD = 0: the trees (A/B)
+#ifndef IA_R16_FOLD
+#define IA_R16_FOLD 1
+#endif
+// CH: the chain (k_screen16r and k_screen16rs take the trees and the old close and flush: their
+// instructions and registers stay what they were, tests/test_lum_shared_host.py test_screen_resources)
+template <bool CH = IA_R16_FOLD>
+__device__ __forceinline__ float fold2(float mn, float a, float b) {
+    return CH ? fminf(fminf(mn, a), b) : fminf(mn, fminf(a, b));
+}
+template <bool CH = IA_R16_FOLD>
+__device__ __forceinline__ float fold4(float mn, const floatx4 &x) {
+    return CH ? fold2<true>(fold2<true>(mn, x[0], x[1]), x[2], x[3])
+              : fminf(fminf(mn, fminf(x[0], x[1])), fminf(x[2], x[3]));
+}
 template <int G, int W>
 __host__ __device__ constexpr int c16_lo() { return 4 * G * W; }   // first chain of wave W
 template <int G, int W>
@@ -269,7 +300,7 @@ __device__ __forceinline__ int s16_aoff(int v, int n, int lane) {
 constexpr int S16_LAG = 3;   // chain c folds chain c - S16_LAG (no MFMA -> VALU pads)
 constexpr int S16_NACC = S16_LAG + 1;
 
-template <int G, int W, int NS>
+template <int G, int W, int NS, bool CH = IA_R16_FOLD>
 __device__ __forceinline__ void r16_stage_s16(const half8 *sb, const half8 (&bq)[NS][2], float (&mn)[NS], int lane) {
     constexpr int NC = c16_count<G, W>();
     const floatx4 zero = {};
@@ -288,9 +319,9 @@ __device__ __forceinline__ void r16_stage_s16(const half8 *sb, const half8 (&bq)
             a[ab ^ 1][1] = sb[s16_aoff(vn, 1, lane)];
         }
         acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[ab][0], bq[k][0], zero, 0, 0, 0);
-        if constexpr (cf >= 0) mn[c16_k<G, W>(cf)] = fminf(mn[c16_k<G, W>(cf)], fminf(acc[fb][0], acc[fb][1]));
+        if constexpr (cf >= 0) mn[c16_k<G, W>(cf)] = fold2<CH>(mn[c16_k<G, W>(cf)], acc[fb][0], acc[fb][1]);
         acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[ab][1], bq[k][1], acc[cb], 0, 0, 0);
-        if constexpr (cf >= 0) mn[c16_k<G, W>(cf)] = fminf(mn[c16_k<G, W>(cf)], fminf(acc[fb][2], acc[fb][3]));
+        if constexpr (cf >= 0) mn[c16_k<G, W>(cf)] = fold2<CH>(mn[c16_k<G, W>(cf)], acc[fb][2], acc[fb][3]);
         if constexpr (IA_R16_PIN) {
             if constexpr (rd) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // DS reads
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                     // MFMA
@@ -302,8 +333,7 @@ __device__ __forceinline__ void r16_stage_s16(const half8 *sb, const half8 (&bq)
     });
     sfor<(NC > S16_LAG ? NC - S16_LAG : 0), NC>([&](auto cc) {
         constexpr int c = decltype(cc)::value;
-        const floatx4 &x = acc[c % S16_NACC];
-        mn[c16_k<G, W>(c)] = fminf(fminf(mn[c16_k<G, W>(c)], fminf(x[0], x[1])), fminf(x[2], x[3]));
+        mn[c16_k<G, W>(c)] = fold4<CH>(mn[c16_k<G, W>(c)], acc[c % S16_NACC]);
     });
 }
 
@@ -329,7 +359,7 @@ __device__ __forceinline__ void r16_stage_s16k(const half8 *sb, const half8 (&bq
         acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[ab], bq[k][0], zero, 0, 0, 0);
         if constexpr (cf >= 0) {
             constexpr int kf = c16_k<G, W>(cf);
-            mn[kf] = fminf(fminf(mn[kf], fminf(acc[fb][0], acc[fb][1])), fminf(acc[fb][2], acc[fb][3]));
+            mn[kf] = fold4(mn[kf], acc[fb]);
         }
         if constexpr (IA_R16_PIN) {
             if constexpr (rd) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
@@ -340,8 +370,7 @@ __device__ __forceinline__ void r16_stage_s16k(const half8 *sb, const half8 (&bq
     });
     sfor<(NC > S16_LAG ? NC - S16_LAG : 0), NC>([&](auto cc) {
         constexpr int c = decltype(cc)::value;
-        const floatx4 &x = acc[c % S16_NACC];
-        mn[c16_k<G, W>(c)] = fminf(fminf(mn[c16_k<G, W>(c)], fminf(x[0], x[1])), fminf(x[2], x[3]));
+        mn[c16_k<G, W>(c)] = fold4(mn[c16_k<G, W>(c)], acc[c % S16_NACC]);
     });
 }
 
@@ -369,20 +398,54 @@ __device__ __forceinline__ void r16_close(int s, int tps, int *smin, float (&mn)
         }
     }
 }
-template <int G, int W, int NS, int TILES = STAGE_TILES, int SPC = SPC_STAGE>
-__device__ __forceinline__ void r16_close_s16(int s, int tps, int *smin, float (&mn)[NS], int lane) {
-    constexpr int T0 = c16_t0<G, W>();
-    const int done = (s + 1) * TILES;
-    if (done % tps == 0) {
-        int *sm = smin + ((done / tps - 1) % SPC) * (G * 32);
+// The 16x16x32 forms' segment close: query block k's minimum over its four 16-lane groups, into
+// sm[16 k + l % 16], then mn = FLT_MAX.  IA_R16_CLOSE = 1: four blocks at a time with the lane
+// swaps (VALU, no LDS round trip).  v_permlane16_swap of (a, b) leaves 16-lane groups (a0, b0, a2,
+// b2) and (a1, b1, a3, b3), whose minimum is (a01, b01, a23, b23); with (c, d) alike,
+// v_permlane32_swap of the two minima leaves (a01, b01, c01, d01) and (a23, b23, c23, d23): their
+// minimum holds block k0 + l / 16's result for query l % 16 in lane l, so the four blocks leave in
+// ONE ds_min_i32 of 64 consecutive words (a last group of fewer blocks repeats its last block
+// and masks the spare lanes).  0: a ds_bpermute pair and a 16-lane ds_min per block, one after
+// the other (the form the lane swaps replaced).  The same minima bit for bit
+#ifndef IA_R16_CLOSE
+#define IA_R16_CLOSE 1
+#endif
+__device__ __forceinline__ float swap_min16(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return fminf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float swap_min32(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return fminf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+template <int NS, bool SW = IA_R16_CLOSE>
+__device__ __forceinline__ void close_blocks_s16(int *sm, float (&mn)[NS], int lane) {
+    if constexpr (SW) {
+        sfor<0, (NS + 3) / 4>([&](auto ii) {
+            constexpr int k0 = 4 * decltype(ii)::value, n = NS - k0 < 4 ? NS - k0 : 4;
+            constexpr int k1 = k0 + (n > 1 ? 1 : 0), k2 = k0 + (n > 2 ? 2 : n - 1), k3 = k0 + n - 1;
+            const float p = swap_min16(mn[k0], mn[k1]);
+            const float q = n > 2 ? swap_min16(mn[k2], mn[k3]) : p;
+            const int m = fkey(swap_min32(p, q));
+            if (n == 4 || lane < 16 * n) lds_min_i32(&sm[k0 * 16 + lane], m);
+        });
+#pragma unroll
+        for (int k = 0; k < NS; ++k) mn[k] = FLT_MAX;
+    } else {
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             float m = fminf(mn[k], __shfl_xor(mn[k], 16));
             m = fminf(m, __shfl_xor(m, 32));
-            if (lane < 16) lds_min_i32(&sm[(T0 + k) * 16 + lane], fkey(m));
+            if (lane < 16) lds_min_i32(&sm[k * 16 + lane], fkey(m));
             mn[k] = FLT_MAX;
         }
     }
+}
+template <int G, int W, int NS, int TILES = STAGE_TILES, int SPC = SPC_STAGE, bool SW = IA_R16_CLOSE>
+__device__ __forceinline__ void r16_close_s16(int s, int tps, int *smin, float (&mn)[NS], int lane) {
+    constexpr int T0 = c16_t0<G, W>();
+    const int done = (s + 1) * TILES;
+    if (done % tps == 0) close_blocks_s16<NS, SW>(smin + ((done / tps - 1) % SPC) * (G * 32) + T0 * 16, mn, lane);
 }
 
 // a workgroup barrier that orders LDS only: __syncthreads()'s release fence would also wait
@@ -411,6 +474,23 @@ __device__ __forceinline__ void wait_stages(int ahead) {
         else wait_stages<NP, MAXA - 1>(ahead);
     }
 }
+
+// Stage timeline of the compact screen (lab builds only: tools/build_variant.sh NAME
+// -DIA_R16_STAMPS=1, read by tools/r16_bench.py --compact --stamps; never in libia.so): wave 0 of
+// ST_BLOCKS blocks spread over the grid stamps s_memtime per stage (< ST_STAGES) at the top of the
+// stage, after its chains, after the close and the flush, after the wait for the next stage and
+// after the barrier.  They are kept in LDS (an inline-asm ds_write, as lds_min_i32, so that the
+// compiler drains no stage in flight for them) and copied out once after the last stage.  The
+// stamps cost wave cycles (each waits for the wave's LDS and scalar returns; measured, a stamped
+// block runs 2.3-2.5 times as long as the others, profiles/screen_fold_stage_stamps.txt): they
+// apportion a stage's time, they are no time themselves
+#ifndef IA_R16_STAMPS
+#define IA_R16_STAMPS 0
+#endif
+#if IA_R16_STAMPS
+constexpr int ST_BLOCKS = 8, ST_STAGES = 64, ST_POINTS = 5;
+__device__ unsigned long long g_r16_stamps[ST_BLOCKS][ST_STAGES][ST_POINTS];
+#endif
 
 // CMP: the compact form (RK_TILE_H8 per tile, one MFMA per chain) with its own geometry: stages
 // of TILES tiles (4 or 8: TILES / 4 stages of the stage map, each 4 consecutive tiles), RK_RING
@@ -481,6 +561,22 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
 #pragma unroll
     for (int k = 0; k < NS; ++k) mn[k] = FLT_MAX;
     const int spc = nstage * TILES / tps;
+#if IA_R16_STAMPS
+    const int st_stride = gridDim.x >= ST_BLOCKS ? gridDim.x / ST_BLOCKS : 1;
+    const int st_slot = CMP && W == 0 && blockIdx.x % st_stride == 0 && blockIdx.x / st_stride < ST_BLOCKS
+                            ? (int)(blockIdx.x / st_stride) : -1;
+    __shared__ unsigned long long st_lds[ST_STAGES * ST_POINTS];
+    auto stamp = [&](int s, int i) {
+        if (st_slot >= 0 && s < ST_STAGES) {
+            typedef __attribute__((address_space(3))) unsigned long long lds_u64;
+            const unsigned long long t = __builtin_amdgcn_s_memtime();
+            const unsigned a = (unsigned)(unsigned long)(lds_u64 *)&st_lds[s * ST_POINTS + i];
+            asm volatile("ds_write_b64 %0, %1" :: "v"(a), "v"(t) : "memory");   // (every lane, one value)
+        }
+    };
+#else
+    auto stamp = [](int, int) {};
+#endif
 #pragma unroll
     for (int s = 0; s < RING - 1; ++s)
         if (s < nstage) issue(s);
@@ -492,6 +588,7 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
     stage_barrier();
     for (int s = 0; s < nstage; ++s) {
         const bool more = s + RING - 1 < nstage;
+        stamp(s, 0);
         if (more) issue(s + RING - 1);   // into the buffer stage s - 1 used (consumed)
         if constexpr (CMP) {
             // (one copy of the stage body: unrolled, the two bodies of an 8-tile stage keep both
@@ -499,10 +596,12 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
 #pragma nounroll
             for (int h = 0; h < MS; ++h)
                 r16_stage_s16k<G, W, NS>(sbuf + (s % RING) * SH8 + h * MH8, bq, mn, lane);
+            stamp(s, 1);
             r16_close_s16<G, W, NS, TILES, SPC>(s, tps, smin, mn, lane);
         } else if constexpr (R16_S16) {
-            r16_stage_s16<G, W, NS>(sbuf + (s % RING) * SH8, bq, mn, lane);
-            r16_close_s16<G, W, NS>(s, tps, smin, mn, lane);
+            // (k_screen16r: the tree fold, the per-block close and the per-element flush it had)
+            r16_stage_s16<G, W, NS, false>(sbuf + (s % RING) * SH8, bq, mn, lane);
+            r16_close_s16<G, W, NS, STAGE_TILES, SPC_STAGE, false>(s, tps, smin, mn, lane);
         } else {
             r16_stage<G, W, NS>(sbuf + (s % RING) * SH8, bq, mn, lane);
             r16_close<G, W, NS>(s, tps, smin, mn, lane);
@@ -513,25 +612,72 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
             if (sg % SPC == SPC - 1 || sg == spc - 1) {
                 stage_barrier();                      // every wave's minima of these segments
                 const int base = sg - sg % SPC, n = sg - base + 1;
-                for (int i = tid; i < G * 32 * n; i += 256) {
-                    const int ql = i / n, k = i - ql * n;
-                    int *e = &smin[k * (G * 32) + ql];
-                    if (q0 + ql < M) {
-                        float *dst = segmin + ((long)(q0 + ql) * nseg + seg0 + base + k);
-                        if constexpr (IA_R16_NTMIN) __builtin_nontemporal_store(fkey_inv(*e), dst);
-                        else *dst = fkey_inv(*e);
+                float *out = segmin + (seg0 + base);
+                if constexpr (!CMP) {
+                    for (int i = tid; i < G * 32 * n; i += 256) {
+                        const int ql = i / n, k = i - ql * n;
+                        int *e = &smin[k * (G * 32) + ql];
+                        if (q0 + ql < M) {
+                            float *dst = segmin + ((long)(q0 + ql) * nseg + seg0 + base + k);
+                            if constexpr (IA_R16_NTMIN) __builtin_nontemporal_store(fkey_inv(*e), dst);
+                            else *dst = fkey_inv(*e);
+                        }
+                        *e = 0x7fffffff;                  // this thread's entries only: no barrier
                     }
-                    *e = 0x7fffffff;                  // this thread's entries only: no barrier
+                } else if (IA_R16_FLUSH && SPC % 4 == 0 && n == SPC && ((nseg | (seg0 + base)) & 3) == 0 &&
+                           ((unsigned long)segmin & 15) == 0) {
+                    // a full group in 16-byte pieces: SPC / 4 lanes per query.  A wave's half (32
+                    // lanes) reads 32 consecutive queries of one staged segment (every bank once:
+                    // the staged stride G * 32 is a multiple of the 32 banks, so the pieces of one
+                    // query must not share a half), 4 segments per lane
+                    constexpr int PC = SPC / 4;
+                    for (int i = tid; i < G * 32 * PC; i += 256) {
+                        const int ql = ((i >> 5) / PC) * 32 + (i & 31), h = (i >> 5) % PC;
+                        int *e = &smin[4 * h * (G * 32) + ql];
+                        floatx4 v;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            v[j] = fkey_inv(e[j * (G * 32)]);
+                            e[j * (G * 32)] = 0x7fffffff;
+                        }
+                        if (q0 + ql < M) {
+                            floatx4 *dst = reinterpret_cast<floatx4 *>(out + (long)(q0 + ql) * nseg + 4 * h);
+                            if constexpr (IA_R16_NTMIN) __builtin_nontemporal_store(v, dst);
+                            else *dst = v;
+                        }
+                    }
+                } else {
+                    // a part's last, shorter group (or minima that are not 16-byte aligned)
+                    for (int i = tid; i < G * 32 * n; i += 256) {
+                        const int ql = i / n, k = i - ql * n;
+                        int *e = &smin[k * (G * 32) + ql];
+                        if (q0 + ql < M) {
+                            float *dst = out + ((long)(q0 + ql) * nseg + k);
+                            if constexpr (IA_R16_NTMIN) __builtin_nontemporal_store(fkey_inv(*e), dst);
+                            else *dst = fkey_inv(*e);
+                        }
+                        *e = 0x7fffffff;                  // this thread's entries only: no barrier
+                    }
                 }
             }
         }
         // stage s + 1 landed: the stages issued after it (RING - 2, fewer at the part's end) may
         // stay in flight
+        stamp(s, 2);
         if constexpr (CMP) wait_stages<NP, RING - 2>(nstage - 2 - s);
         else if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (RING - 2)) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        stamp(s, 3);
         stage_barrier();   // (every wave's reads of stage s done: its buffer is refilled next)
+        stamp(s, 4);
     }
+#if IA_R16_STAMPS
+    if (st_slot >= 0) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int i = lane; i < ST_STAGES * ST_POINTS; i += 64)
+            (&g_r16_stamps[st_slot][0][0])[i] = i / ST_POINTS < nstage ? st_lds[i] : 0ull;
+    }
+#endif
 }
 
 // grid: (nchunks x split rounded up to 8) x groups, XCD-aware (all groups of a part share
@@ -647,8 +793,9 @@ __device__ __forceinline__ void r16_body_s(const half8 *__restrict__ db16, half8
         const bool more = s + R16_RING - 1 < nstage;
         if (more) issue(s + R16_RING - 1);
         if constexpr (R16_S16) {
-            r16_stage_s16<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
-            r16_close_s16<G, W, NS>(s, tps, smin, mn, lane);
+            // (as k_screen16r: the tree fold and the per-block close they had)
+            r16_stage_s16<G, W, NS, false>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
+            r16_close_s16<G, W, NS, STAGE_TILES, SPC_STAGE, false>(s, tps, smin, mn, lane);
         } else {
             r16_stage<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
             r16_close<G, W, NS>(s, tps, smin, mn, lane);
@@ -795,7 +942,8 @@ constexpr int W_SPB_MAX = IA_R16W_SPB;  // segments per workgroup (LDS minima)
 constexpr int W_LAG = 2;               // query blocks between an MFMA pair and its fold
 
 __device__ __forceinline__ void w_fold(const floatx4 &x, const floatx4 &y, float &mn) {
-    mn = fminf(fminf(mn, fminf(x[0], x[1])), fminf(fminf(x[2], x[3]), fminf(fminf(y[0], y[1]), fminf(y[2], y[3]))));
+    if constexpr (IA_R16_FOLD) mn = fold4(fold4(mn, x), y);   // one dependent chain: four v_min3_f32
+    else mn = fminf(fminf(mn, fminf(x[0], x[1])), fminf(fminf(x[2], x[3]), fminf(fminf(y[0], y[1]), fminf(y[2], y[3]))));
 }
 
 // one tile (two 16-row blocks: a[0..1] = block 0 MFMA 0..1, a[2..3] = block 1) against the 2G
@@ -896,14 +1044,7 @@ __global__ __launch_bounds__(512, 4) void k_screen16w(const half8 *__restrict__ 
                 w_tile<NQB>(a[s], qs, mn, lane);
                 const int jj = jw + j;
                 if (((jj + 1) & (tps - 1)) == 0 || j + 1 == tpw) {   // the wave leaves a segment
-                    int *sm0 = smin + (jj >> lts) * (NQB * 16);
-#pragma unroll
-                    for (int k = 0; k < NQB; ++k) {
-                        float m = fminf(mn[k], __shfl_xor(mn[k], 16));
-                        m = fminf(m, __shfl_xor(m, 32));
-                        if (lane < 16) lds_min_i32(&sm0[k * 16 + lane], fkey(m));
-                        mn[k] = FLT_MAX;
-                    }
+                    close_blocks_s16<NQB>(smin + (jj >> lts) * (NQB * 16), mn, lane);
                 }
             }
         });
@@ -1355,6 +1496,21 @@ int ia_screen_resources(int which, int *lds, int *vgprs) {
     *vgprs = at.numRegs;
     return IA_OK;
 }
+
+#if IA_R16_STAMPS
+/* lab builds only (IA_R16_STAMPS): the stage stamps of the compact screen launches since the last
+ * call, [ST_BLOCKS = 8][ST_STAGES = 64][ST_POINTS = 5] s_memtime values (0: not written), then
+ * cleared; synchronises the device */
+int ia_lab_r16_stamps(unsigned long long *out) {
+    IA_ARG(out, "ia_lab_r16_stamps: null buffer");
+    IA_HIP(hipDeviceSynchronize());
+    IA_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_r16_stamps), sizeof(g_r16_stamps)));
+    void *p = nullptr;
+    IA_HIP(hipGetSymbolAddress(&p, HIP_SYMBOL(g_r16_stamps)));
+    IA_HIP(hipMemset(p, 0, sizeof(g_r16_stamps)));
+    return IA_OK;
+}
+#endif
 
 int ia_diag_set_r16_form(int form) {
     const int prev = r16_form();

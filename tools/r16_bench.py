@@ -39,6 +39,10 @@ def main():
                     '(torch.cuda._sleep: the product\'s gaps between screens); not counted.  A comma '
                     'list times every M once per value')
     ap.add_argument('--compact', action='store_true', help='the compact screen (ia_diag_screen16k)')
+    ap.add_argument('--stamps', action='store_true', help='with --compact and a library built with '
+                    '-DIA_R16_STAMPS=1 (tools/build_variant.sh): one more launch per M whose stage stamps '
+                    '(wave 0 of 8 blocks, s_memtime at 5 points per stage) are reduced to the median cycles '
+                    'and share per phase.  The stamps cost cycles themselves: shares, not times')
     args = ap.parse_args()
     Ms = [int(x) for x in args.M.split(',')]
     dev = torch.device('cuda', 0)
@@ -100,6 +104,36 @@ def main():
                         'db_gbs': db_bytes / (us * 1e-6) / 1e9, 'compact': args.compact,
                         'minima': minima, 'sleep': sleep, 'lib': os.environ.get('IA_LIB_PATH', 'libia.so')})
             print(json.dumps(out[-1]), flush=True)
+        if args.stamps:
+            print(json.dumps(stage_stamps(lib, run, M)), flush=True)
+
+
+PHASES = ('issue+chains', 'close+flush', 'vmcnt wait', 'barrier', 'loop')
+
+
+def stage_stamps(lib, run, M):
+    """One launch's stage stamps (csrc/ia_screen16r.hip IA_R16_STAMPS): per phase the median cycles
+    over the stamped (block, stage) pairs and its share of the stage (top to next top)."""
+    assert hasattr(lib, 'ia_lab_r16_stamps'), 'a library built with -DIA_R16_STAMPS=1'
+    fn = lib.ia_lab_r16_stamps
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p]
+    buf = np.zeros((8, 64, 5), dtype=np.uint64)
+    _ia.check(fn(buf.ctypes.data), 'clear')
+    run()
+    _ia.check(fn(buf.ctypes.data), 'ia_lab_r16_stamps')
+    t = buf.astype(np.int64)
+    d = []
+    for b in range(8):
+        n = int((t[b, :, 0] != 0).sum())               # stages this block stamped
+        for s in range(n - 1):                         # (the last stage has no next top)
+            x = list(t[b, s]) + [t[b, s + 1, 0]]
+            d.append([x[i + 1] - x[i] for i in range(5)])
+    d = np.asarray(d, dtype=np.float64)
+    med = np.median(d, axis=0)
+    return {'M': M, 'stamped_stages': len(d), 'stage_cycles_median': float(np.median(d.sum(1))),
+            'phase_median_cycles': dict(zip(PHASES, [float(x) for x in med])),
+            'phase_share_of_sum': dict(zip(PHASES, [round(float(x), 4) for x in d.sum(0) / d.sum()])),
+            'lib': os.environ.get('IA_LIB_PATH', 'libia.so')}
 
 
 if __name__ == '__main__':
