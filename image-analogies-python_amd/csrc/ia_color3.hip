@@ -743,21 +743,34 @@ __global__ __launch_bounds__(256) void k_query3r(Img3 Bsm, Img3 Blg, Img3 Bpsm, 
 // each DB tile read once per wave)
 // 7 query tiles per group (a c3 wave's <= 213 queries: one group; LDS 77 KiB, two workgroups
 // per CU: the grid's ~450 workgroups in one round instead of two)
-// (screen3r_body: the body of k_screen3r, one job, and k_screen3rb, a batch)
 constexpr int S3R_QG = 7;
-__device__ __forceinline__ void screen3r_body(const half8 *__restrict__ db16, int ntiles,
-                                              const half8 *__restrict__ q16, int M, int tpw,
-                                              float *__restrict__ smin) {
-    __shared__ half8 qsh[S3R_QG * R3_TILE];
+// The row-tile loop of the R16c screens: the workgroup's nq staged query tiles (qsh) against this
+// wave's row tiles.  QS says whose queries the staged tiles are: q0(j), tile j's first query,
+// and smin(j), the minima it writes to.  S3One: consecutive tiles of one job (k_screen3r, and
+// k_screen3rb per job of a batch); S3Tab: tiles of several jobs passing one database, looked
+// up per staged entry (k_screen3rs).  QS is passed by value and its members are the
+// expressions the kernels had in place, term for term: k_screen3r's and k_screen3rb's
+// instructions are those of the bodies written out (checked instruction by instruction on the
+// gfx950 assembly, profiles/screen_loop_isa.txt; tests/test_gpu_color3_shared.py pins the registers)
+struct S3One {
+    int qt0;
+    float *__restrict__ sm;
+    __device__ __forceinline__ int q0(int j) const { return (qt0 + j) * 32; }
+    __device__ __forceinline__ float *smin(int) const { return sm; }
+};
+struct S3Tab {
+    const int *q0_sh;                // per staged entry: its first query
+    const gptr<float> *smin_sh;      // and its job's minima (gptr: global accesses)
+    __device__ __forceinline__ int q0(int j) const { return q0_sh[j]; }
+    __device__ __forceinline__ float *smin(int j) const { return smin_sh[j].p; }
+};
+template <typename QS>
+__device__ __forceinline__ void screen3r_rows(const half8 *__restrict__ db16, int ntiles, int M, int tpw,
+                                              const half8 *qsh, int nq, const QS qs) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int qt0 = blockIdx.y * S3R_QG;
-    const int QT = (M + 31) / 32;
-    const int nq = QT - qt0 < S3R_QG ? QT - qt0 : S3R_QG;
-    for (int i = threadIdx.x; i < nq * R3_TILE; i += 256) qsh[i] = q16[(long)qt0 * R3_TILE + i];
-    __syncthreads();
     const floatx16 zero = {};
     int t = blockIdx.x * tpw * 4 + wv;
-    if (t >= ntiles) return;   // (after the only barrier)
+    if (t >= ntiles) return;   // (after the last barrier)
     half8 a[R3_MFMA], n[R3_MFMA];
 #pragma unroll
     for (int c = 0; c < R3_MFMA; ++c) a[c] = db16[(long)t * R3_TILE + c * 64 + lane];
@@ -793,14 +806,26 @@ __device__ __forceinline__ void screen3r_body(const half8 *__restrict__ db16, in
             }
             mn0 = fminf(mn0, __shfl_xor(mn0, 32));
             mn1 = fminf(mn1, __shfl_xor(mn1, 32));
-            const int q0 = (qt0 + j) * 32 + lane, q1 = (qt0 + j1) * 32 + lane;
-            if (lane < 32 && q0 < M) smin[(long)q0 * c3_stride(ntiles) + t] = mn0;
-            if (lane < 32 && j1 != j && q1 < M) smin[(long)q1 * c3_stride(ntiles) + t] = mn1;
+            const int q0 = qs.q0(j) + lane, q1 = qs.q0(j1) + lane;
+            if (lane < 32 && q0 < M) qs.smin(j)[(long)q0 * c3_stride(ntiles) + t] = mn0;
+            if (lane < 32 && j1 != j && q1 < M) qs.smin(j1)[(long)q1 * c3_stride(ntiles) + t] = mn1;
         }
         if (!more) break;
 #pragma unroll
         for (int c = 0; c < R3_MFMA; ++c) a[c] = n[c];
     }
+}
+// (screen3r_body: the body of k_screen3r, one job, and k_screen3rb, a batch)
+__device__ __forceinline__ void screen3r_body(const half8 *__restrict__ db16, int ntiles,
+                                              const half8 *__restrict__ q16, int M, int tpw,
+                                              float *__restrict__ smin) {
+    __shared__ half8 qsh[S3R_QG * R3_TILE];
+    const int qt0 = blockIdx.y * S3R_QG;
+    const int QT = (M + 31) / 32;
+    const int nq = QT - qt0 < S3R_QG ? QT - qt0 : S3R_QG;
+    for (int i = threadIdx.x; i < nq * R3_TILE; i += 256) qsh[i] = q16[(long)qt0 * R3_TILE + i];
+    __syncthreads();   // (the only barrier)
+    screen3r_rows(db16, ntiles, M, tpw, qsh, nq, S3One{qt0, smin});
 }
 __global__ __launch_bounds__(256, 2) void k_screen3r(const half8 *__restrict__ db16, int ntiles,
                                                      const half8 *__restrict__ q16, int M, int tpw,
@@ -1106,9 +1131,9 @@ __global__ __launch_bounds__(256, 2) void k_screen3rb(const C3Job *__restrict__ 
 // The screen of a batch whose jobs share databases (G groups < K jobs): block (x, y, group z)
 // stages up to S3R_QG consecutive entries of the group's list of n_g QT query tiles (entry e: tile
 // e % QT of the group's job e / QT, each from its own job's q16) and walks the group's row
-// tiles once for all of them, as screen3r_body does for one job's tiles (its row-tile loop,
-// kept as a copy: a body shared with k_screen3r / k_screen3rb changes their instructions);
-// every entry's minima go to its own job's smin.  It waits for nothing.
+// tiles once for all of them, as screen3r_body does for one job's tiles: the same row-tile loop
+// (screen3r_rows) after a staging of its own (per-entry sources, two barriers); every entry's
+// minima go to its own job's smin.  It waits for nothing.
 // entries per workgroup of a list of ne: its ceil(ne / S3R_QG) query groups, evenly filled
 __host__ __device__ constexpr int s3rs_per(int ne) {
     return (ne + (ne + S3R_QG - 1) / S3R_QG - 1) / ((ne + S3R_QG - 1) / S3R_QG);
@@ -1122,7 +1147,6 @@ __global__ __launch_bounds__(256, 2) void k_screen3rs(const C3Job *__restrict__ 
     __shared__ gptr<float> smin_sh[S3R_QG];        // its job's minima (gptr: global accesses)
     __shared__ int q0_sh[S3R_QG];             // and its first query
     const C3Job &G = jobs[blockIdx.z];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int QT = (M + 31) / 32;
     // the list's ceil(ne / S3R_QG) query groups in equal parts (8 entries: 4 + 4, not 7 + 1: the
     // launch is as long as its longest workgroup)
@@ -1143,50 +1167,7 @@ __global__ __launch_bounds__(256, 2) void k_screen3rs(const C3Job *__restrict__ 
     }
     __syncthreads();
     const gptr<const half8> db16g = G.gdbr;
-    const auto *__restrict__ db16 = db16g.p;
-    const floatx16 zero = {};
-    int t = blockIdx.x * tpw * 4 + wv;
-    if (t >= ntiles) return;   // (after the last barrier)
-    half8 a[R3_MFMA], n[R3_MFMA];
-#pragma unroll
-    for (int c = 0; c < R3_MFMA; ++c) a[c] = db16[(long)t * R3_TILE + c * 64 + lane];
-    for (int it = 0; it < tpw; ++it, t += 4) {
-        const int tn = t + 4;
-        const bool more = it + 1 < tpw && tn < ntiles;
-        if (more)
-#pragma unroll
-            for (int c = 0; c < R3_MFMA; ++c) n[c] = db16[(long)tn * R3_TILE + c * 64 + lane];
-        for (int j = 0; j < nq; j += 2) {
-            const int j1 = j + 1 < nq ? j + 1 : j;
-            const half8 *qb0 = qsh + j * R3_TILE + lane, *qb1 = qsh + j1 * R3_TILE + lane;
-            half8 b0[R3_MFMA], b1[R3_MFMA];
-#pragma unroll
-            for (int c = 0; c < R3_MFMA; ++c) {
-                b0[c] = qb0[c * 64];
-                b1[c] = qb1[c * 64];
-            }
-            floatx16 acc0 = zero, acc1 = zero;
-#pragma unroll
-            for (int c = 0; c < R3_MFMA; ++c) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[c], b0[c], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[c], b1[c], acc1, 0, 0, 0);
-            }
-            float mn0 = acc0[0], mn1 = acc1[0];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) {
-                mn0 = fminf(mn0, acc0[i]);
-                mn1 = fminf(mn1, acc1[i]);
-            }
-            mn0 = fminf(mn0, __shfl_xor(mn0, 32));
-            mn1 = fminf(mn1, __shfl_xor(mn1, 32));
-            const int q0 = q0_sh[j] + lane, q1 = q0_sh[j1] + lane;
-            if (lane < 32 && q0 < M) smin_sh[j].p[(long)q0 * c3_stride(ntiles) + t] = mn0;
-            if (lane < 32 && j1 != j && q1 < M) smin_sh[j1].p[(long)q1 * c3_stride(ntiles) + t] = mn1;
-        }
-        if (!more) break;
-#pragma unroll
-        for (int c = 0; c < R3_MFMA; ++c) a[c] = n[c];
-    }
+    screen3r_rows(db16g.p, ntiles, M, tpw, qsh, nq, S3Tab{q0_sh, smin_sh});
 }
 template <bool FUSE>
 __global__ __launch_bounds__(256) void k_exact3b(const C3Job *__restrict__ jobs, int t, int y_lo, int M,

@@ -23,8 +23,9 @@
 // 8, a whole part of the finest levels, so that a query's minima leave in runs of 32 B, two
 // 16-byte stores by two lanes of different wave halves).  k_screen16r and k_screen16rs keep
 // the tree fold, a ds_bpermute close per block and a per-element flush (k_screen16r's
-// instructions and registers are pinned, tests/test_lum_shared_host.py, and k_screen16rs is its
-// copy); k_screen16c and k_screen16w take the new fold and close.
+// instructions and registers are pinned, tests/test_lum_shared_host.py, and k_screen16rs runs
+// the same body, r16_body, under another query policy); k_screen16c and k_screen16w take the
+// new fold and close.
 #include "ia_internal.h"
 #include "ia_rot16.h"
 #include "../../include/ia_diag.h"
@@ -495,12 +496,60 @@ __device__ unsigned long long g_r16_stamps[ST_BLOCKS][ST_STAGES][ST_POINTS];
 // CMP: the compact form (RK_TILE_H8 per tile, one MFMA per chain) with its own geometry: stages
 // of TILES tiles (4 or 8: TILES / 4 stages of the stage map, each 4 consecutive tiles), RK_RING
 // buffers, RK_SPC staged segments; nstage counts stages of TILES tiles, s0 the part's first
-// stage in the stage map's units
-template <int G, int W, bool CMP = false, int TILES = STAGE_TILES>
-__device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *sbuf, int *smin,
-                                         const StageMap &sm, long chunk, int s0, int nstage, int tps,
-                                         const half8 *__restrict__ q16, float *__restrict__ segmin,
-                                         long seg0, long nseg, int q0, int M) {
+// stage in the stage map's units.  NEWFOLD: the 64-slot 16x16x32 form's fold and close
+// QS: whose queries the workgroup's G tiles are, a policy passed by value.
+//   qrows(ql)   the array local query ql's row (q16 layout) lies in;
+//   TILE_MASK   which part of a tile's index counts in a row's index there: -1, all of it (the
+//               tiles' rows are one array), or 0, none (an array per tile).  The body derives
+//               BM = 2 TILE_MASK + 1, the same for 16-query blocks, two per tile: -1 for one job,
+//               1 for the table (block B is rows 16 (B & 1) .. of tile B / 2);
+//   valid(ql)   local query ql is a real one;
+//   out(seg)    the origin of a group of segments from seg on.  Its type is the policy's own (a
+//               pointer for one job, the segment number for the table) and opaque to the body,
+//               which only hands it to
+//   at(out, ql, nseg, k)   where query ql's minimum of the group's k-th segment goes;
+//   aligned16() (the compact form) 16-byte stores may be taken from out().
+// R16One: one job, G consecutive tiles from query q0 of its q16 and segmin (k_screen16r,
+// k_screen16c).  R16Tab: tile i's rows, minima and number of real queries from a table in LDS
+// (k_screen16rs: tiles of several jobs passing one database).
+// What a policy must preserve: k_screen16r's and k_screen16c's instructions are those of the body
+// they had to themselves (tests/test_lum_shared_host.py pins the registers).  For that, R16One's
+// members are the expressions that body had in their places, term for term and in the same
+// association (out() is taken once per group, as it was), the row index is written out in the body
+// (not a member's result: the address is formed before members are inlined), the policy is the
+// first parameter (it travels in registers, not through memory), and q16 and segmin stay
+// __restrict__, here and in r16_one, through which the one-job kernels enter.  Checked on the
+// gfx950 assembly, instruction by instruction, for every instance: profiles/screen_loop_isa.txt
+struct R16One {
+    const half8 *__restrict__ q16;   // the group's first query row
+    float *__restrict__ segmin;
+    int q0, M;
+    static constexpr int TILE_MASK = -1;
+    __device__ __forceinline__ const half8 *qrows(int) const { return q16; }
+    __device__ __forceinline__ bool valid(int ql) const { return q0 + ql < M; }
+    __device__ __forceinline__ float *out(long seg) const { return segmin + seg; }
+    __device__ __forceinline__ float *at(float *o, int ql, long nseg, int k) const {
+        return o + ((long)(q0 + ql) * nseg + k);
+    }
+    __device__ __forceinline__ bool aligned16() const { return ((unsigned long)segmin & 15) == 0; }
+};
+struct R16Tab {
+    const half8 *const *qt;   // per tile: its 32 query rows,
+    float *const *sp;         // its segmin rows
+    const int *lim;           // and how many of them are real queries
+    static constexpr int TILE_MASK = 0;
+    __device__ __forceinline__ const half8 *qrows(int ql) const { return qt[ql >> 5]; }
+    __device__ __forceinline__ bool valid(int ql) const { return (ql & 31) < lim[ql >> 5]; }
+    __device__ __forceinline__ long out(long seg) const { return seg; }
+    __device__ __forceinline__ float *at(long o, int ql, long nseg, int k) const {
+        return sp[ql >> 5] + ((long)(ql & 31) * nseg + o + k);
+    }
+};
+
+template <int G, int W, bool CMP = false, int TILES = STAGE_TILES, bool NEWFOLD = false, typename QS>
+__device__ __forceinline__ void r16_body(const QS qs, const half8 *__restrict__ db16, half8 *sbuf, int *smin,
+                                         const StageMap &sm, long chunk, int s0, int nstage, int tps, long seg0,
+                                         long nseg) {
     static_assert(!CMP || RK_BUILT, "the compact form needs the 16x16x32 shape at P = 3");
     static_assert(TILES % STAGE_TILES == 0 && (CMP || TILES == STAGE_TILES), "stage geometry");
     constexpr int RING = CMP ? RK_RING : R16_RING, SPC = CMP ? RK_SPC : SPC_STAGE;
@@ -513,18 +562,22 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     half8 bq[NS][CMP ? 1 : R16_S16 ? 2 : R16_MFMA];
+    constexpr int BM = 2 * QS::TILE_MASK + 1;   // TILE_MASK for 16-query blocks (two per tile)
     if constexpr (CMP) {
-        // query block T + k, lane l: query 16 (T + k) + l % 16, compact slots 8 (l / 16) .. + 7
+        // query block B = T + k, lane l: query 16 B + l % 16, compact slots 8 (l / 16) .. + 7
 #pragma unroll
-        for (int k = 0; k < NS; ++k)
-            bq[k][0] = q16[(long)((c16_t0<G, W>() + k) * 16 + (lane & 15)) * Q16_ROW + RK_Q_F16 / 8 + (lane >> 4)];
+        for (int k = 0; k < NS; ++k) {
+            const int B = c16_t0<G, W>() + k;
+            bq[k][0] = qs.qrows(B * 16)[(long)((B & BM) * 16 + (lane & 15)) * Q16_ROW + RK_Q_F16 / 8 + (lane >> 4)];
+        }
     } else if constexpr (R16_S16) {
-        // query block T + k, lane l: query 16 (T + k) + l % 16, slots 32 n + 8 (l / 16) .. + 7,
+        // query block B = T + k, lane l: query 16 B + l % 16, slots 32 n + 8 (l / 16) .. + 7,
         // i.e. the half8 (l / 16) % 2 * R16_MFMA + 2n + (l / 16) / 2 of its q16 row
         const int q = lane >> 4, c = lane & 15;
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
-            const half8 *p = q16 + (long)((c16_t0<G, W>() + k) * 16 + c) * Q16_ROW + (q & 1) * R16_MFMA + (q >> 1);
+            const int B = c16_t0<G, W>() + k;
+            const half8 *p = qs.qrows(B * 16) + (long)((B & BM) * 16 + c) * Q16_ROW + (q & 1) * R16_MFMA + (q >> 1);
             bq[k][0] = p[0];
             bq[k][1] = p[2];
         }
@@ -532,7 +585,8 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
         const int j = lane & 31, h = lane >> 5;
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
-            const half8 *p = q16 + (long)((T0 + k) * 32 + j) * Q16_ROW + h * R16_MFMA;
+            const int T = T0 + k;
+            const half8 *p = qs.qrows(T * 32) + (long)((T & QS::TILE_MASK) * 32 + j) * Q16_ROW + h * R16_MFMA;
 #pragma unroll
             for (int m = 0; m < R16_MFMA; ++m) bq[k][m] = p[m];
         }
@@ -599,9 +653,11 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
             stamp(s, 1);
             r16_close_s16<G, W, NS, TILES, SPC>(s, tps, smin, mn, lane);
         } else if constexpr (R16_S16) {
-            // (k_screen16r: the tree fold, the per-block close and the per-element flush it had)
-            r16_stage_s16<G, W, NS, false>(sbuf + (s % RING) * SH8, bq, mn, lane);
-            r16_close_s16<G, W, NS, STAGE_TILES, SPC_STAGE, false>(s, tps, smin, mn, lane);
+            // (NEWFOLD = false, k_screen16r and k_screen16rs: the tree fold, the per-block close and
+            // the per-element flush they had.  Moving either to the chain fold and the lane-swap
+            // close is that one template argument at its r16_body call)
+            r16_stage_s16<G, W, NS, NEWFOLD>(sbuf + (s % RING) * SH8, bq, mn, lane);
+            r16_close_s16<G, W, NS, STAGE_TILES, SPC_STAGE, NEWFOLD>(s, tps, smin, mn, lane);
         } else {
             r16_stage<G, W, NS>(sbuf + (s % RING) * SH8, bq, mn, lane);
             r16_close<G, W, NS>(s, tps, smin, mn, lane);
@@ -612,47 +668,43 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
             if (sg % SPC == SPC - 1 || sg == spc - 1) {
                 stage_barrier();                      // every wave's minima of these segments
                 const int base = sg - sg % SPC, n = sg - base + 1;
-                float *out = segmin + (seg0 + base);
-                if constexpr (!CMP) {
-                    for (int i = tid; i < G * 32 * n; i += 256) {
-                        const int ql = i / n, k = i - ql * n;
-                        int *e = &smin[k * (G * 32) + ql];
-                        if (q0 + ql < M) {
-                            float *dst = segmin + ((long)(q0 + ql) * nseg + seg0 + base + k);
-                            if constexpr (IA_R16_NTMIN) __builtin_nontemporal_store(fkey_inv(*e), dst);
-                            else *dst = fkey_inv(*e);
-                        }
-                        *e = 0x7fffffff;                  // this thread's entries only: no barrier
-                    }
-                } else if (IA_R16_FLUSH && SPC % 4 == 0 && n == SPC && ((nseg | (seg0 + base)) & 3) == 0 &&
-                           ((unsigned long)segmin & 15) == 0) {
-                    // a full group in 16-byte pieces: SPC / 4 lanes per query.  A wave's half (32
-                    // lanes) reads 32 consecutive queries of one staged segment (every bank once:
-                    // the staged stride G * 32 is a multiple of the 32 banks, so the pieces of one
-                    // query must not share a half), 4 segments per lane
-                    constexpr int PC = SPC / 4;
-                    for (int i = tid; i < G * 32 * PC; i += 256) {
-                        const int ql = ((i >> 5) / PC) * 32 + (i & 31), h = (i >> 5) % PC;
-                        int *e = &smin[4 * h * (G * 32) + ql];
-                        floatx4 v;
+                const auto out = qs.out(seg0 + base);   // the group's first segment
+                // the compact form's full group leaves in 16-byte pieces (aligned minima); `wide` is
+                // false at compile time for the other forms, whose wide branch is not instantiated
+                bool wide = false;
+                if constexpr (CMP && IA_R16_FLUSH && SPC % 4 == 0)
+                    wide = n == SPC && ((nseg | (seg0 + base)) & 3) == 0 && qs.aligned16();
+                if (wide) {
+                    if constexpr (CMP) {
+                        // SPC / 4 lanes per query.  A wave's half (32 lanes) reads 32 consecutive
+                        // queries of one staged segment (every bank once: the staged stride G * 32
+                        // is a multiple of the 32 banks, so the pieces of one query must not share
+                        // a half), 4 segments per lane
+                        constexpr int PC = SPC / 4;
+                        for (int i = tid; i < G * 32 * PC; i += 256) {
+                            const int ql = ((i >> 5) / PC) * 32 + (i & 31), h = (i >> 5) % PC;
+                            int *e = &smin[4 * h * (G * 32) + ql];
+                            floatx4 v;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            v[j] = fkey_inv(e[j * (G * 32)]);
-                            e[j * (G * 32)] = 0x7fffffff;
-                        }
-                        if (q0 + ql < M) {
-                            floatx4 *dst = reinterpret_cast<floatx4 *>(out + (long)(q0 + ql) * nseg + 4 * h);
-                            if constexpr (IA_R16_NTMIN) __builtin_nontemporal_store(v, dst);
-                            else *dst = v;
+                            for (int j = 0; j < 4; ++j) {
+                                v[j] = fkey_inv(e[j * (G * 32)]);
+                                e[j * (G * 32)] = 0x7fffffff;
+                            }
+                            if (qs.valid(ql)) {
+                                floatx4 *dst = reinterpret_cast<floatx4 *>(qs.at(out, ql, nseg, 0) + 4 * h);
+                                if constexpr (IA_R16_NTMIN) __builtin_nontemporal_store(v, dst);
+                                else *dst = v;
+                            }
                         }
                     }
                 } else {
-                    // a part's last, shorter group (or minima that are not 16-byte aligned)
+                    // per element: the 64-slot forms, and the compact form's last, shorter group of
+                    // a part (or minima that are not 16-byte aligned)
                     for (int i = tid; i < G * 32 * n; i += 256) {
                         const int ql = i / n, k = i - ql * n;
                         int *e = &smin[k * (G * 32) + ql];
-                        if (q0 + ql < M) {
-                            float *dst = out + ((long)(q0 + ql) * nseg + k);
+                        if (qs.valid(ql)) {
+                            float *dst = qs.at(out, ql, nseg, k);
                             if constexpr (IA_R16_NTMIN) __builtin_nontemporal_store(fkey_inv(*e), dst);
                             else *dst = fkey_inv(*e);
                         }
@@ -678,6 +730,26 @@ __device__ __forceinline__ void r16_body(const half8 *__restrict__ db16, half8 *
             (&g_r16_stamps[st_slot][0][0])[i] = i / ST_POINTS < nstage ? st_lds[i] : 0ull;
     }
 #endif
+}
+
+// One job's body: its q16 and segmin alias nothing else the body touches (the table form cannot
+// promise that: the tiles of one job share its segmin)
+template <int G, int W, bool CMP = false, int TILES = STAGE_TILES>
+__device__ __forceinline__ void r16_one(const half8 *__restrict__ db16, half8 *sbuf, int *smin,
+                                        const StageMap &sm, long chunk, int s0, int nstage, int tps,
+                                        const half8 *__restrict__ q16, float *__restrict__ segmin,
+                                        long seg0, long nseg, int q0, int M) {
+    r16_body<G, W, CMP, TILES>(R16One{q16, segmin, q0, M}, db16, sbuf, smin, sm, chunk, s0, nstage, tps, seg0, nseg);
+}
+
+// f(W) for the calling wave's index W in the workgroup, as a compile-time constant (as sfor)
+template <typename F>
+__device__ __forceinline__ void r16_wave(F &&f) {
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wv == 0) f(std::integral_constant<int, 0>{});
+    else if (wv == 1) f(std::integral_constant<int, 1>{});
+    else if (wv == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
 }
 
 // grid: (nchunks x split rounded up to 8) x groups, XCD-aware (all groups of a part share
@@ -713,11 +785,9 @@ __global__ __launch_bounds__(256, IA_R16_OCC) void k_screen16r(const half8 *__re
     const long seg0 = (long)chunk * spc + (long)half * (spc >> lsp);
     const int q0 = group * G * 32;
     const int s0 = half * nstage;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (wv == 0) r16_body<G, 0>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
-    else if (wv == 1) r16_body<G, 1>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
-    else if (wv == 2) r16_body<G, 2>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
-    else r16_body<G, 3>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+    r16_wave([&](auto w) {
+        r16_one<G, decltype(w)::value>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+    });
 }
 
 // ---- the shared form (k_screen16rs): a batch whose jobs share rotated databases ----------
@@ -738,95 +808,10 @@ __host__ __device__ inline void sq_split(int nT, int qg, int &first, int &count)
     count = base + (qg < rem ? 1 : 0);
 }
 
-// r16_body's row loop as a copy (as k_screen3rs has one: k_screen16r, k_screen16c and
-// k_screen16w keep their instructions whatever changes here): the query operands and the
-// minima's destinations are per tile (qt, sp, lim in LDS: tile i's 32 query rows, its segmin
-// rows and how many of them are real queries)
-template <int G, int W>
-__device__ __forceinline__ void r16_body_s(const half8 *__restrict__ db16, half8 *sbuf, int *smin,
-                                           const StageMap &sm, long chunk, int s0, int nstage, int tps,
-                                           const half8 *const *qt, float *const *sp, const int *lim,
-                                           long seg0, long nseg) {
-    constexpr int NS = R16_S16 ? c16_ns<G, W>() : bal_ns(G, W);
-    constexpr int T0 = bal_t0(G, W);
-    constexpr int TH8 = R16_TILE_H8, SH8 = STAGE_TILES * TH8, NP = SH8 / 256;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    half8 bq[NS][R16_S16 ? 2 : R16_MFMA];
-    if constexpr (R16_S16) {
-        // query block B = T + k is rows 16 (B % 2) .. + 15 of tile B / 2 (operands as r16_body)
-        const int q = lane >> 4, c = lane & 15;
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            constexpr int B0 = c16_t0<G, W>();
-            const half8 *p = qt[(B0 + k) >> 1] + (long)(((B0 + k) & 1) * 16 + c) * Q16_ROW + (q & 1) * R16_MFMA + (q >> 1);
-            bq[k][0] = p[0];
-            bq[k][1] = p[2];
-        }
-    } else {
-        const int j = lane & 31, h = lane >> 5;
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const half8 *p = qt[T0 + k] + (long)j * Q16_ROW + h * R16_MFMA;
-#pragma unroll
-            for (int m = 0; m < R16_MFMA; ++m) bq[k][m] = p[m];
-        }
-    }
-    auto issue = [&](int s) {
-        const half8 *src = db16 + (stage_lrow(sm, chunk, s0 + s) >> 5) * TH8 + W * 64 + lane;
-        half8 *dst = sbuf + (s % R16_RING) * SH8 + W * 64;
-#pragma unroll
-        for (int k = 0; k < NP; ++k)
-            __builtin_amdgcn_global_load_lds((const void *)(src + k * 256), (void *)(dst + k * 256), 16, 0, 2);
-    };
-    float mn[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) mn[k] = FLT_MAX;
-    const int spc = nstage * STAGE_TILES / tps;
-#pragma unroll
-    for (int s = 0; s < R16_RING - 1; ++s)
-        if (s < nstage) issue(s);
-    if (nstage > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (R16_RING - 2)) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stage_barrier();
-    for (int s = 0; s < nstage; ++s) {
-        const bool more = s + R16_RING - 1 < nstage;
-        if (more) issue(s + R16_RING - 1);
-        if constexpr (R16_S16) {
-            // (as k_screen16r: the tree fold and the per-block close they had)
-            r16_stage_s16<G, W, NS, false>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
-            r16_close_s16<G, W, NS, STAGE_TILES, SPC_STAGE, false>(s, tps, smin, mn, lane);
-        } else {
-            r16_stage<G, W, NS>(sbuf + (s % R16_RING) * SH8, bq, mn, lane);
-            r16_close<G, W, NS>(s, tps, smin, mn, lane);
-        }
-        const int done = (s + 1) * STAGE_TILES;
-        if (done % tps == 0) {
-            const int sg = done / tps - 1;
-            if (sg % SPC_STAGE == SPC_STAGE - 1 || sg == spc - 1) {
-                stage_barrier();
-                const int base = sg - sg % SPC_STAGE, n = sg - base + 1;
-                for (int i = tid; i < G * 32 * n; i += 256) {
-                    const int ql = i / n, k = i - ql * n;
-                    int *e = &smin[k * (G * 32) + ql];
-                    const int tl = ql >> 5, l = ql & 31;
-                    if (l < lim[tl]) {
-                        float *dst = sp[tl] + ((long)l * nseg + seg0 + base + k);
-                        if constexpr (IA_R16_NTMIN) __builtin_nontemporal_store(fkey_inv(*e), dst);
-                        else *dst = fkey_inv(*e);
-                    }
-                    *e = 0x7fffffff;
-                }
-            }
-        }
-        if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NP * (R16_RING - 2)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stage_barrier();
-    }
-}
-
 // grid: (nchunks x split rounded up to 8) x nqg, XCD-aware as k_screen16r (all query groups of
-// a part share blockIdx % 8); nqg: the query groups of every DB group, in group order
+// a part share blockIdx % 8); nqg: the query groups of every DB group, in group order.  The row
+// loop is r16_body's under R16Tab: tile i's query rows, segmin rows and number of real queries
+// (qt, sp, lim) are staged in LDS before any stage is in flight
 template <int G>
 __global__ __launch_bounds__(256, IA_R16_OCC) void k_screen16rs(const XJob *__restrict__ jobs,
                                                        const int *__restrict__ gtab, int nchunks, int ch,
@@ -874,11 +859,9 @@ __global__ __launch_bounds__(256, IA_R16_OCC) void k_screen16rs(const XJob *__re
     const long seg0 = (long)chunk * spc + (long)half * (spc >> lsp);
     const int s0 = half * nstage;
     __syncthreads();   // the tile table (before any stage is in flight)
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (wv == 0) r16_body_s<G, 0>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qt, sp, lim, seg0, nseg);
-    else if (wv == 1) r16_body_s<G, 1>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qt, sp, lim, seg0, nseg);
-    else if (wv == 2) r16_body_s<G, 2>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qt, sp, lim, seg0, nseg);
-    else r16_body_s<G, 3>(db16, sbuf, smin, sm, chunk, s0, nstage, tps, qt, sp, lim, seg0, nseg);
+    r16_wave([&](auto w) {
+        r16_body<G, decltype(w)::value>(R16Tab{qt, sp, lim}, db16, sbuf, smin, sm, chunk, s0, nstage, tps, seg0, nseg);
+    });
 }
 
 // the compact screen (ia_rot16.h RK_*; one job): k_screen16r's grid, parts and minima over the
@@ -906,12 +889,11 @@ __global__ __launch_bounds__(256, IA_RK_OCC) void k_screen16c(const half8 *__res
     const long seg0 = (long)chunk * spc + (long)half * (spc >> lsp);
     const int q0 = group * G * 32;
     const int s0 = half * nstage * (TILES / STAGE_TILES);
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if constexpr (RK_BUILT) {
-        if (wv == 0) r16_body<G, 0, true, TILES>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
-        else if (wv == 1) r16_body<G, 1, true, TILES>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
-        else if (wv == 2) r16_body<G, 2, true, TILES>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
-        else r16_body<G, 3, true, TILES>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0, nseg, q0, M);
+        r16_wave([&](auto w) {
+            r16_one<G, decltype(w)::value, true, TILES>(dbk, sbuf, smin, sm, chunk, s0, nstage, tps, qg, segmin, seg0,
+                                                        nseg, q0, M);
+        });
     }
 }
 
